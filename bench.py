@@ -7,10 +7,17 @@ fused LM-head loss -> backward -> (RCCL gradient all-reduce, overlapped) -> Adam
 configs[1]: bf16, seq_len 32, per-GPU batch 256, `full` mode (all 247.8 M parameters trained), dropout active.
 Weak scaling: per-GPU batch is fixed, global batch = 256*N.
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes work of its own beyond the timed
+steps: the CPU baseline and the distance phase of the roofline (below).  --dump-outputs DIR writes what the last timed step
+handed its caller (losses, perplexity, accuracy, code indices, reconstructed ids) and a fixed, seeded sample of the parameters
+after it as DIR/<name>.npy (float32 / float64); the inputs depend on the arguments only, so two builds compare output for output.
+
 Extra objects on the line:
   roofline     the VQ distance+argmin kernel (vq_dist_packed_kernel), timed with HIP events around every launch of the timed
-               region on the stream it runs on; bound = f32 MFMA (exact-f32 distances), HBM figure beside it
-  cpu_baseline oracle/step_oracle.py (CPU f32 restatement, "port") timed on this host's cores, rank 0 at N=1 only
+               region on the stream it runs on; bound = f32 MFMA (exact-f32 distances, SURVEY.md §8d), HBM figure beside it;
+               roofline.distance_phase (9 further steps) with --full only
+  cpu_baseline oracle/step_oracle.py (CPU f32 restatement, "port") timed on this host's cores, rank 0 at N=1 only, with --full
+               (or --cpu-same-batch)
   clock_mhz    the shader clock held over the timed region (kvq_clock_probe stamps bracket it); roofline.frac_at_clock prices the
                kernel against the peak at THAT clock, so lines from different boxes / rounds can be compared
   vs_cpu_port  value / cpu_baseline.value -- NOT a like-for-like speed-up (GPU batch 256 bf16 against the CPU restatement at
@@ -70,7 +77,38 @@ def parse():
                     "(TokenCache.batch: index_select + the ids' stable sort), as models/*/Trainer.train() does: `value_pack_in_step`")
     ap.add_argument("--path", default="engine", choices=["engine", "autograd"],
                     help="engine = kvq.engine.TrainEngine (explicit fwd/bwd over flat buffers); autograd = kvq.bert + torch autograd")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure what a plain run leaves out: the CPU baseline (cpu_baseline, "
+                    "vs_cpu_port) and the distance phase of the roofline (roofline.distance_phase)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the outputs of the last timed "
+                    "step and a seeded sample of the parameters after it as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_PARAM_STRIDE = 256        # --dump-outputs: about one parameter element in 256 (~1 M floats = 4 MB at bert-base)
+
+
+def dump_outputs(path, out, model):
+    """What the last timed step handed its caller, as float32 (floating point) or float64 (integer) .npy files, plus a fixed
+    sample of the parameters the step left behind: per parameter in name order, numel // DUMP_PARAM_STRIDE (at least one)
+    positions drawn from a generator seeded with 0."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        if not isinstance(v, torch.Tensor):
+            continue
+        t = v.detach()
+        t = t.float() if t.is_floating_point() else t.double()
+        np.save(os.path.join(path, f"{k}.npy"), t.cpu().numpy())
+    rng = np.random.default_rng(0)
+    parts = []
+    for _, p in sorted(model.named_parameters(), key=lambda kv: kv[0]):
+        flat = p.detach().reshape(-1)
+        pick = torch.from_numpy(np.sort(rng.integers(0, flat.numel(), max(flat.numel() // DUMP_PARAM_STRIDE, 1)))).to(flat.device)
+        parts.append(flat.index_select(0, pick).float().cpu())
+    np.save(os.path.join(path, "params_sample.npy"), torch.cat(parts).numpy())
 
 
 def spawn_ranks(a):
@@ -159,16 +197,19 @@ def main():
         # (what the word-embedding gradient needs) packed into one tensor, resident in HBM like the ids themselves
         pool = [(ids, mask, engine.pack_batch(ids, mask)) for ids, mask in pool]
 
+    last = {}                          # the outputs of the latest step, as its caller receives them (--dump-outputs)
+
     def one_step(i):
         ids, mask = pool[i % len(pool)][:2]
         if a.bagon:
             _, _, d, dm, pack = pool[i % len(pool)]
-            out = engine.train_step(ids, mask, prepared=pack, dec_ids=d, dec_mask=dm)
+            out = last["out"] = engine.train_step(ids, mask, prepared=pack, dec_ids=d, dec_mask=dm)
             return out["loss_recon"], 0.0
         if engine is not None:
-            out = engine.train_step(ids, mask, prepared=pool[i % len(pool)][2])
+            out = last["out"] = engine.train_step(ids, mask, prepared=pool[i % len(pool)][2])
             return out["loss_recon"], out["loss_vq"]           # (added on the host after the timed region: no extra launch per step)
-        loss_vq, perp, _idx, loss_recon, acc, _recon = model.forward_loss(ids, mask)
+        loss_vq, perp, idx, loss_recon, acc, recon = model.forward_loss(ids, mask)
+        last["out"] = dict(loss_vq=loss_vq, perplexity=perp, indices=idx, loss_recon=loss_recon, acc=acc, recon_ids=recon)
         loss = loss_recon + loss_vq
         if sync is not None:
             sync.zero_grad()
@@ -202,6 +243,8 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     final_loss = float(loss[0]) + float(loss[1]) if isinstance(loss, tuple) else float(loss)
+    if a.dump_outputs and rank == 0:                           # before any further step can move the parameters
+        dump_outputs(a.dump_outputs, last["out"], model)
     rccl_ranks, exposed_ms = 1, 0.0
     if grouped:
         probe = torch.ones(1, device=dev)
@@ -245,7 +288,8 @@ def main():
     # (kvq_vq_set_variant(0): the quantiser forward is an eager interlude between the step's graphs, so nothing is re-captured);
     # the event pair then brackets the distance kernel only -- same code, same operands, same place in the step
     dist_phase_ms = None
-    if engine is not None and vq is not None and not grouped and os.environ.get("KVQ_VQ_FUSED", "1") != "0" and n_ev and not a.no_distance_phase:
+    if (a.full and engine is not None and vq is not None and not grouped and os.environ.get("KVQ_VQ_FUSED", "1") != "0" and n_ev
+            and not a.no_distance_phase):
         lib.kvq_vq_set_variant(0)
         one_step(a.warmup + a.steps)
         torch.cuda.synchronize()
@@ -394,7 +438,7 @@ def main():
                 "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": step_flops / step_s / 1e12 / BF16_MFMA_PEAK_TFLOPS,
                 "frac_at_clock": (step_flops / step_s / 1e12 / (BF16_MFMA_PEAK_TFLOPS * at_clock)) if at_clock else None, "traffic": None},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and (a.full or a.cpu_same_batch) and not a.no_cpu_baseline:
             from oracle import step_oracle
             cfg = dict(BERT_BASE) if a.model == "bert-base-uncased" else None
             if cfg is None:

@@ -192,3 +192,26 @@ def test_bench_refuses_to_report_a_number_for_a_job_size_it_did_not_run():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode != 0 and "refusing" in (r.stderr + r.stdout) and '"metric"' not in r.stdout
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_parameter_sample(tmp_path):
+    """bench.py --dump-outputs: every tensor output as float32 (floating point) or float64 (integer) .npy, and the same
+    parameter positions on every run, so that two builds can be compared output for output."""
+    import bench                                    # (the repository root is on sys.path: tests/conftest.py)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(64, 48), torch.nn.LayerNorm(48))
+    out = {"loss_recon": torch.tensor(1.5), "loss_vq": None, "indices": torch.arange(12).reshape(3, 4, 1),
+           "recon_ids": torch.tensor([[30521, 7]]), "acc_per_sentence": torch.rand(3, dtype=torch.bfloat16)}
+    bench.dump_outputs(str(tmp_path / "a"), out, model)
+    bench.dump_outputs(str(tmp_path / "b"), out, model)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["acc_per_sentence.npy", "indices.npy", "loss_recon.npy", "params_sample.npy", "recon_ids.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    assert np.load(tmp_path / "a" / "indices.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "a" / "recon_ids.npy"), [[30521.0, 7.0]])
+    n_sample = sum(max(p.numel() // bench.DUMP_PARAM_STRIDE, 1) for p in model.parameters())
+    sample = np.load(tmp_path / "a" / "params_sample.npy")
+    assert sample.shape == (n_sample,) and sample.dtype == np.float32
+    assert set(sample.tolist()) <= set(torch.cat([p.detach().reshape(-1) for p in model.parameters()]).tolist())

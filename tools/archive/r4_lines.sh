@@ -4,7 +4,7 @@ set -uo pipefail
 out=gpurun_out/r4g
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf "$out"; mkdir -p "$out"
-python bench.py > "$out/bench_line.json" 2> "$out/bench.err"; echo "default rc=$?"
+python bench.py --full > "$out/bench_line.json" 2> "$out/bench.err"; echo "default rc=$?"
 python bench.py --bagon --no-cpu-baseline > "$out/bench_line_bagon.json" 2> "$out/bench_bagon.err"; echo "bagon rc=$?"
 python bench.py --seq-len 12 --batch 128 --no-cpu-baseline --steps 50 > "$out/bench_line_s12_b128.json" 2> "$out/s12.err"; echo "s12 rc=$?"
 KVQ_OWN_GEMM=0 python bench.py --seq-len 12 --batch 128 --no-cpu-baseline --steps 50 > "$out/bench_line_s12_b128_library_gemm.json" 2> "$out/s12lib.err"; echo "s12 lib rc=$?"

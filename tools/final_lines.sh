@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # the tracked bench lines of a round, all from one box and one build:  tools/final_lines.sh <tag>   ->  gpurun_out/<tag>_lines/*.json
 tag="${1:-r03}"; out="gpurun_out/${tag}_lines"; mkdir -p "$out"
-python bench.py > "$out/bench_line.json" 2> "$out/bench_line.err"
+python bench.py --full > "$out/bench_line.json" 2> "$out/bench_line.err"
 python bench.py --no-cpu-baseline --codes 8192 > "$out/bench_line_k8192.json" 2> "$out/k8192.err"
 python bench.py --no-cpu-baseline --factors 9 > "$out/bench_line_9factors.json" 2> "$out/9f.err"
 python bench.py --no-cpu-baseline --fp8 --factors 9 > "$out/bench_line_fp8_9factors.json" 2> "$out/fp8.err"

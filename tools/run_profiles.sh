@@ -20,5 +20,5 @@ echo "counter passes done"
 VQ_K=8192 timeout -k 10 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch_k8192" -- python tools/vq_only.py > "$out/pmc_fetch_k8192.log" 2>&1
 VQ_K=8192 timeout -k 10 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/pmc_write_k8192" -- python tools/vq_only.py > "$out/pmc_write_k8192.log" 2>&1
 echo "K = 8192 traffic passes done"
-timeout -k 10 300 python bench.py > "$out/bench_line.json" 2> "$out/bench.err"
+timeout -k 10 300 python bench.py --full > "$out/bench_line.json" 2> "$out/bench.err"
 tail -c 600 "$out/bench_line.json"
