@@ -892,19 +892,17 @@ struct Milestones {
     long long at[8];
     int n;
 };
-// phase 1: lr / bias corrections of the step about to be applied; phase 2: step += 1; 3: both (kvq_step_state_advance)
-__global__ void step_state_advance_kernel(StepState* st, float lr0, float gamma, Milestones ms, float beta1, float beta2, int phase) {
+// step += 1 and the lr / bias corrections of that step (kvq_step_state_advance)
+__global__ void step_state_advance_kernel(StepState* st, float lr0, float gamma, Milestones ms, float beta1, float beta2) {
     const unsigned long long t = st->step + 1;             // the step now being applied (1-based)
-    if (phase & 1) {
-        int k = 0;
-        for (int i = 0; i < ms.n; ++i) k += ((long long)(t - 1) >= ms.at[i]) ? 1 : 0;   // MultiStepLR ticked once per finished step
-        double lr = lr0;
-        for (int i = 0; i < k; ++i) lr *= (double)gamma;
-        st->lr = (float)lr;
-        st->bc1 = (float)(1.0 - pow((double)beta1, (double)t));
-        st->bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)t));
-    }
-    if (phase & 2) st->step = t;
+    int k = 0;
+    for (int i = 0; i < ms.n; ++i) k += ((long long)(t - 1) >= ms.at[i]) ? 1 : 0;   // MultiStepLR ticked once per finished step
+    double lr = lr0;
+    for (int i = 0; i < k; ++i) lr *= (double)gamma;
+    st->lr = (float)lr;
+    st->bc1 = (float)(1.0 - pow((double)beta1, (double)t));
+    st->bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)t));
+    st->step = t;
 }
 
 // out = x * keep / (1-p) with the Philox mask of (seed, site): the dropout behind the embedding LayerNorm (modeling_bert.py:58,
@@ -2787,27 +2785,16 @@ int kvq_adam_step_dev_fp8(float* p, const void* g, float* m, float* v, float* vm
                        reinterpret_cast<const float*>(reinterpret_cast<const char*>(step_state) + 8), stream, f8);
 }
 
-static int step_state_launch(void* step_state, float lr0, float gamma, const int64_t* milestones, int n_milestones, float beta1,
-                             float beta2, int phase, void* stream, const char* who) {
+int kvq_step_state_advance(void* step_state, float lr0, float gamma, const int64_t* milestones, int n_milestones, float beta1,
+                           float beta2, void* stream) {
     KVQ_REQUIRE(step_state && n_milestones >= 0 && n_milestones <= 8 && (n_milestones == 0 || milestones),
-                "%s: bad argument (at most 8 milestones)", who);
+                "kvq_step_state_advance: bad argument (at most 8 milestones)");
     Milestones ms = {};
     ms.n = n_milestones;
     for (int i = 0; i < n_milestones; ++i) ms.at[i] = milestones[i];
     hipLaunchKernelGGL(step_state_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (StepState*)step_state, lr0, gamma, ms, beta1,
-                       beta2, phase);
+                       beta2);
     return check_launch("step_state_advance_kernel");
-}
-int kvq_step_state_advance(void* step_state, float lr0, float gamma, const int64_t* milestones, int n_milestones, float beta1,
-                           float beta2, void* stream) {
-    return step_state_launch(step_state, lr0, gamma, milestones, n_milestones, beta1, beta2, 3, stream, "kvq_step_state_advance");
-}
-int kvq_step_state_prepare(void* step_state, float lr0, float gamma, const int64_t* milestones, int n_milestones, float beta1,
-                           float beta2, void* stream) {
-    return step_state_launch(step_state, lr0, gamma, milestones, n_milestones, beta1, beta2, 1, stream, "kvq_step_state_prepare");
-}
-int kvq_step_state_commit(void* step_state, void* stream) {
-    return step_state_launch(step_state, 0.f, 0.f, nullptr, 0, 0.f, 0.f, 2, stream, "kvq_step_state_commit");
 }
 
 size_t kvq_embed_grad_workspace_bytes(int64_t N, int H) {

@@ -273,38 +273,38 @@ class _StepGraphs:
         # no garbage collection while a capture is open (what torch.cuda.graph does as well): a collected cycle may own HIP
         # objects -- an older engine's kept hipGraphs -- whose destruction is not permitted while this thread captures
         import gc
-        gc.collect()
         gc_was_on = gc.isenabled()
-        gc.disable()
-        torch.cuda.synchronize(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
         step0 = eng._step_host
-        ok = False
-        with torch.cuda.stream(side):
-            eng._cap = self
-            try:
-                # thread-local capture mode: the process group's helper threads (gloo copies, the RCCL watchdog's event queries)
-                # keep issuing HIP calls on their own streams while this thread captures
-                self.graphs[0].capture_begin(capture_error_mode="thread_local")
-                eng._prepared = dict(enc=self.sorted, dec=self.dec[2:4] if self.dec else None)
-                dkw = dict(dec_ids=self.dec[0], dec_mask=self.dec[1], target_ids=self.dec[4]) if self.dec else {}
-                self.out = eng.forward_backward(self.ids, self.mask, training=eng.model.training, compute_grads=True, fuse_optimizer=True,
-                                                **dkw)
-                eng.optimizer_step()
-                self.graphs[-1].capture_end()
-                ok = True
-            finally:
-                eng._cap = None
-                eng._prepared = None
-                eng._step_host = step0      # capturing ran no captured kernel: the device step state did not move either
-                if not ok:                  # close the capture that was open when the error struck
-                    try:
-                        eng._adam_join()    # (a forked side stream must be back in the origin stream before the capture can end)
-                        self.graphs[-1].capture_end()
-                    except Exception:
-                        pass
-                if gc_was_on:
-                    gc.enable()
+        try:
+            gc.collect()
+            gc.disable()
+            torch.cuda.synchronize(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                eng._cap = self
+                ok = False
+                try:
+                    # thread-local capture mode: the process group's helper threads (gloo copies, the RCCL watchdog's event
+                    # queries) keep issuing HIP calls on their own streams while this thread captures
+                    self.graphs[0].capture_begin(capture_error_mode="thread_local")
+                    eng._prepared = dict(enc=self.sorted, dec=self.dec[2:4] if self.dec else None)
+                    dkw = dict(dec_ids=self.dec[0], dec_mask=self.dec[1], target_ids=self.dec[4]) if self.dec else {}
+                    self.out = eng.forward_backward(self.ids, self.mask, training=eng.model.training, compute_grads=True, **dkw)
+                    eng.optimizer_step()
+                    self.graphs[-1].capture_end()
+                    ok = True
+                finally:
+                    eng._cap = None
+                    eng._prepared = None
+                    eng._step_host = step0      # capturing ran no captured kernel: the device step state did not move either
+                    if not ok:                  # close the capture that was open when the error struck
+                        try:
+                            self.graphs[-1].capture_end()
+                        except Exception:
+                            pass
+        finally:
+            if gc_was_on:
+                gc.enable()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
 
@@ -408,34 +408,19 @@ class TrainEngine:
         if os.environ.get("KVQ_GEMM_TILE"):       # "NxK:tile;NxK:tile" (A/B runs on the GPU box)
             self._TILE_OVERRIDE = {tuple(int(v) for v in e.split(":")[0].split("x")): e.split(":")[1]
                                    for e in os.environ["KVQ_GEMM_TILE"].split(";") if e}
-        self._own_epi = os.environ.get("KVQ_OWN_EPI", "1") != "0"     # A/B switch: 0 = activations as separate kernels behind the GEMMs
         # round 5: dropout + residual of a BertSelfOutput / BertOutput block in the dense layer's epilogue, LayerNorm alone behind it
         # (8.2 us instead of 11.9: one tensor read, one written).  Bit-identical -- and only worth it WITHOUT dropout: the Philox
         # rounds of 6 M elements are ~5 us of vector-ALU time per SIMD, which the LayerNorm kernel hides behind its loads and a
         # GEMM epilogue does not (same-box traces, profiles/r05_gemm_ceiling.md: +7 us per GEMM against -3.7 us per LayerNorm).
         # "eval" (default): steps without dropout (validation / test stages, model.forward); "1": always (tests); "0": never.
         self._fuse_dropres = os.environ.get("KVQ_FUSE_DROPRES", "eval")
-        # weight gradients of a whole layer as ONE grouped launch of csrc/kvq_gemm2.hip (KVQ_OWN_WGRAD=0: library + split-K slabs)
-        self._own_wgrad = self._own_fwd and os.environ.get("KVQ_OWN_WGRAD", "1") != "0" and self.dtype == torch.bfloat16
+        # weight gradients as grouped launches of csrc/kvq_gemm2.hip, two layers per launch where they fit one round of the CUs
+        # (_flush_wgrads)
+        self._own_wgrad = self._own_fwd and self.dtype == torch.bfloat16
         self._wg_items, self._wg_keep = [], []
-        self._wg_pair = os.environ.get("KVQ_WG_PAIR", "1") != "0"     # A/B switch: 0 = one grouped launch per layer (128 x 256 tiles)
-        self._red_pair = os.environ.get("KVQ_RED_PAIR", "1") != "0"   # A/B switch: 0 = the batched reductions stay per layer
         # LM head + the loss' forward statistics in one kernel (see _forward_backward): built and parity-tested in round 2, and
         # 0.08 ms/step SLOWER than library GEMM + kvq_ce_forward (18.55 against 18.47 ms, gpurun_out/ab16.log): opt-in
         self._own_lmce = os.environ.get("KVQ_OWN_LMCE", "0") == "1"
-        # opt-in (KVQ_EARLY_ADAM=1): Adam for a layer's parameters as soon as their gradients are final, on a side stream beside the
-        # rest of backward (one GPU only).  The update is pure HBM streaming and the GEMMs beside it live on L2 -> LDS bandwidth,
-        # yet on MI355X the step got SLOWER: 18.88 against 18.18 ms (gpurun_out/ab6.log), and 19.5-19.8 against 18.86 with the
-        # Adam grid capped at 128-1024 workgroups (ab7.log) -- like the side-stream weight gradients, a second kernel on the
-        # CUs costs the one-workgroup-per-CU GEMMs more than the overlap returns.  Off by default.
-        self._early_adam = os.environ.get("KVQ_EARLY_ADAM", "0") == "1"
-        self.adam_stream = torch.cuda.Stream(device=dev) if self._early_adam else None
-        self._fuse_opt, self._adam_hi, self._adam_forked = False, 0, False
-        # opt-in (KVQ_WG_STREAM=1): weight-gradient GEMMs on a side stream.  Measured on MI355X with the step replayed from
-        # hipGraphs: 23.6 ms/step against 22.5 ms on one stream -- two concurrent hipBLASLt kernels share CUs and L2 badly
-        self.wg_stream = torch.cuda.Stream(device=dev) if os.environ.get("KVQ_WG_STREAM", "0") == "1" else None
-        self._wg_pending = False
-        self._wg_keep_step = []
         self.use_graph = os.environ.get("KVQ_GRAPH", "1") != "0"
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
@@ -764,7 +749,7 @@ class TrainEngine:
         """Tile of the fused-activation GEMMs (they exist for 256 x 192 and 128 x 256), or None when the plain GEMM on its best
         tile + the separate activation kernel (one pass over [M, N]: ~3 us + 4 bytes per element at ~3 TB/s) is modelled cheaper --
         outputs too small to give half the CUs one of the large tiles."""
-        if not (self._own_fwd and self._own_epi and self.dtype == torch.bfloat16):
+        if not (self._own_fwd and self.dtype == torch.bfloat16):
             return None
         t = nnops.pick_tile(M, N, K, candidates=("256x192", "128x256"))
         plain = nnops.tile_cost_us(nnops.pick_tile(M, N, K), M, N, K) + 3.0 + M * N * 4 / 3e6
@@ -777,7 +762,7 @@ class TrainEngine:
         fl = self.flat
         W, b = fl.w(wname), fl.w(bname)
         gamma, beta = fl.w32(gname), fl.w32(betaname)
-        if (self._fuse_dropres == "1" or (self._fuse_dropres == "eval" and p_drop == 0.0)) and self._own_fwd and self._own_epi \
+        if (self._fuse_dropres == "1" or (self._fuse_dropres == "eval" and p_drop == 0.0)) and self._own_fwd \
                 and self.dtype == torch.bfloat16 \
                 and not (self.fp8 and wname in self._w8_index) and a.is_contiguous() and resid.is_contiguous() \
                 and nnops.gemm_mfma_ok(a, W, None, "nt", b):
@@ -838,40 +823,23 @@ class TrainEngine:
         if not items:
             return True
         t256 = self._wg_tiles(items, 256, 256)
-        if not force and self._wg_pair and self.wg_stream is None and len(items) <= self._WG_MAX // 2 and 2 * t256 <= 256:
+        if not force and len(items) <= self._WG_MAX // 2 and 2 * t256 <= 256:
             return False                                   # another layer like this one still fits the same round
         tile = "256x256" if self._wg_tiles(items, 128, 256) > 256 and t256 <= 320 else "128x256"
-        if self.wg_stream is not None:
-            # KVQ_WG_STREAM=1: the layer's weight gradients run on a side stream while the main stream goes on with the next
-            # layer's backward chain (nothing there reads them); joined at the end of backward / before an all-reduce
-            self.wg_stream.wait_stream(torch.cuda.current_stream(self.dev))
-            with torch.cuda.stream(self.wg_stream):
-                for i in range(0, len(items), self._WG_MAX):
-                    nnops.gemm_grouped(items[i:i + self._WG_MAX], "tn", tile)
-            self._wg_pending = True
-            self._wg_keep_step += self._wg_keep            # operands stay alive until the join
-        else:
-            for i in range(0, len(items), self._WG_MAX):
-                nnops.gemm_grouped(items[i:i + self._WG_MAX], "tn", tile)
+        for i in range(0, len(items), self._WG_MAX):
+            nnops.gemm_grouped(items[i:i + self._WG_MAX], "tn", tile)
         self._wg_items, self._wg_keep = [], []
         return True
 
-    def _join_wgrads(self):
-        if self._wg_pending:
-            torch.cuda.current_stream(self.dev).wait_stream(self.wg_stream)
-            self._wg_pending = False
-        self._wg_keep_step = []
-
     def _flush_reductions(self, force=True):
         """Launch the queued batched reductions and (see _flush_wgrads) the queued weight gradients; True if none stay queued."""
-        done = self._flush_wgrads(force)
-        if not done and self._red_pair:
+        if not self._flush_wgrads(force):
             return False                       # ... and the small sums wait with them: one launch per two layers as well
         if self._red_items:
             nnops.reduce_batch(self._red_items)       # (round 5: on a side stream, joined with the weight gradients, the step was
                                                       #  0.5 ms SLOWER -- profiles/r05_gemm_ceiling.md)
         self._red_items, self._red_keep = [], []
-        return done
+        return True
 
     def _defer_colsum(self, x, dst, cols=None):
         part = nnops.colsum_partial(x, cols)
@@ -896,14 +864,8 @@ class TrainEngine:
         return g_y, g_resid
 
     def _wgrad(self, gy, x, out):
-        """gW = gy^T x.  Nothing on the way to the next layer's gradient needs it; with KVQ_WG_STREAM=1 it runs on a side stream
-        next to the input-gradient GEMM (a fork / join inside the captured hipGraph, joined by the layer's batched reduction).
-        Off by default: it measured 5 % slower than one stream."""
-        return self._wgrad_on_current_stream(gy, x, out)
-
-    def _wgrad_on_current_stream(self, gy, x, out):
-        """bf16: a launch of its own when the output alone fills half the CUs with 256 x 256 tiles (the LM head / all-layer
-        cross-K/V weight gradients), else queued for the layer's grouped launch; both contract over ALL tokens per tile (no split-K).
+        """gW = gy^T x.  bf16: a launch of its own when the output alone fills half the CUs with 256 x 256 tiles (the LM head /
+        all-layer cross-K/V weight gradients), else queued for the layer's grouped launch; both contract over ALL tokens per tile (no split-K).
         A token count that is not a multiple of 64 (the MFMA kernel's k-tile: 100 sentences x 12 tokens, the last batch of an
         epoch) is zero-padded first -- zero rows of gy / x add nothing -- so that the step stays on the MFMA kernels; only what
         cannot be padded in 16-byte pieces goes to the any-shape kernel."""
@@ -1143,11 +1105,7 @@ class TrainEngine:
         else:
             self._wg_done_lo = lo
         if not self._dp:
-            if self._fuse_opt and lo < self._adam_hi:
-                self._adam_early(lo, self._adam_hi)
-                self._adam_hi = lo
             return
-        self._join_wgrads()
         ranges = []
         while self._pending_hi - self.chunk >= lo:
             ranges.append((self._pending_hi - self.chunk, self._pending_hi))
@@ -1170,7 +1128,6 @@ class TrainEngine:
 
     def _eager(self, fn):
         """Run fn now; while a step is being captured it also becomes an eager launch between two graphs of the replay."""
-        self._adam_join()                  # a captured graph ends here: no side-stream work may be left open in it
         if self._cap is not None:
             self._cap.interlude(fn)
         else:
@@ -1229,18 +1186,14 @@ class TrainEngine:
     # one training step
     # ------------------------------------------------------------------------------------------------------------
     def forward_backward(self, input_ids, attention_mask, training=True, compute_grads=True, dec_ids=None, dec_mask=None,
-                         want_logits=False, quantizer_training=None, fuse_optimizer=False, stop_after_quantizer=False,
-                         defer_backward=False, target_ids=None):
+                         want_logits=False, quantizer_training=None, stop_after_quantizer=False, defer_backward=False, target_ids=None):
         """Forward (+ backward when compute_grads).  Returns dict(loss_recon, loss_vq, perplexity, acc, acc_per_sentence,
         recon_ids, indices [, logits]).  dec_ids / dec_mask: the decoder's own input (Bagon.forward takes one, and the Bagon step
         tokenises and perturbs the two sides separately, models/bagon/Trainer.py:78-96; default = the encoder's).  target_ids:
         what the loss and the accuracy score the logits against (default = the decoder's input, as models/bagon/Trainer.py:103-110
         and models/shelgon3/Trainer.py:94-101 do).
-        fuse_optimizer (train_step only; optimizer_step() MUST follow): parameters are updated while backward still runs.
         defer_backward (with compute_grads=False): the forward's activations stay alive and out["_resume"] can be handed to
         backward_from() once the gradient of the returned logits is known (kvq.engine.engine_autograd_forward)."""
-        self._fuse_opt = bool(fuse_optimizer) and compute_grads and self._early_adam and not self._dp
-        self._adam_hi, self._adam_forked = self.flat.n, False
         self._stop_after_quantizer = bool(stop_after_quantizer) and not compute_grads
         S = max(input_ids.shape[1], dec_ids.shape[1] if dec_ids is not None else 0)
         if S > (128 if self.dtype == torch.bfloat16 else 32):
@@ -1323,7 +1276,6 @@ class TrainEngine:
         self._red_items, self._red_keep = [], []
         self._wg_items, self._wg_keep = [], []
         self._sorted = resume["sorted_ids"]
-        self._fuse_opt = False
         self._g_vq_ext = (g_loss_vq.detach().to(torch.float32).reshape(()) if g_loss_vq is not None
                           else torch.zeros((), dtype=torch.float32, device=self.dev)) if self.has_vq else None
         nnops.set_seed_offset(self._state)          # the step count has not moved: backward regenerates the forward's dropout masks
@@ -1454,8 +1406,6 @@ class TrainEngine:
             g_ext = yield out               # suspended here until backward_from() sends d L / d logits
 
         # ---------------- backward ----------------
-        if self._fuse_opt:      # lr / bias corrections of the step about to be applied; the step COUNT (dropout seed offset) stays
-            nnops.step_state_advance(self._state, self.lr, self.gamma, self.milestones, self.betas[0], self.betas[1], phase="prepare")
         tr = fl.trainable
         g_scale = self._g_recon
         if g_ext is not None:
@@ -1538,7 +1488,6 @@ class TrainEngine:
                 enc_saved[i] = None
             self._emb_bwd("enc.emb.", g_x, emb_saved)
         self._flush_reductions()
-        self._join_wgrads()
         return out
 
     def _buf(self, name, shape, dtype):
@@ -1693,35 +1642,9 @@ class TrainEngine:
                                     vmax=fl.vmax[a:b] if fl.vmax is not None else None,
                                     shadow=fl.shadow[a:b] if fl.shadow is not fl.master else None)
 
-    def _adam_early(self, lo, hi):
-        """[lo, hi) of the flat buffer is final and no kernel of this step reads those weights any more: update it beside backward."""
-        main = torch.cuda.current_stream(self.dev)
-        self.adam_stream.wait_stream(main)
-        with torch.cuda.stream(self.adam_stream):
-            self._adam_ranges(lo, hi)
-        self._adam_forked = True
-
-    def _adam_join(self):
-        if self._adam_forked:
-            torch.cuda.current_stream(self.dev).wait_stream(self.adam_stream)
-            self._adam_forked = False
-
     def optimizer_step(self):
         fl = self.flat
         b1, b2 = self.betas
-        if self._fuse_opt:
-            self._fuse_opt = False
-            self._wg_done_lo = fl.n
-            if self.vq_ema:
-                self._eager(self._ema_step)
-            self._step_host += 1
-            self._adam_ranges(0, self._adam_hi)           # the head of the buffer: embeddings, final only now
-            self._adam_hi = fl.n
-            self._adam_aux()
-            self._adam_join()
-            nnops.step_state_commit(self._state)
-            self._after_update()
-            return
         cut = 0
         if self._dp:
             cut = self._pending_hi                    # [0, cut) has not been sent yet (embedding gradients)
@@ -1866,8 +1789,7 @@ class TrainEngine:
         self._prepared = prep
         dkw = dict(dec_ids=dec[0], dec_mask=dec[1], target_ids=dec[2]) if dec is not None else {}
         try:
-            out = self.forward_backward(input_ids, attention_mask, training=self.model.training, compute_grads=True, fuse_optimizer=True,
-                                        **dkw)
+            out = self.forward_backward(input_ids, attention_mask, training=self.model.training, compute_grads=True, **dkw)
         finally:
             self._prepared = None
         self.optimizer_step()
@@ -1929,9 +1851,8 @@ class TrainEngine:
                 self._works, self._works_late = [], []
             self._pending_hi = self.flat.n
         self._wg_done_lo = self.flat.n
-        self._red_items, self._red_keep, self._wg_pending = [], [], False
-        self._wg_items, self._wg_keep, self._wg_keep_step = [], [], []
-        self._fuse_opt, self._adam_forked, self._adam_hi = False, False, self.flat.n
+        self._red_items, self._red_keep = [], []
+        self._wg_items, self._wg_keep = [], []
 
     def eval_step(self, input_ids, attention_mask, dec_ids=None, dec_mask=None, target_ids=None):
         return self.forward_backward(input_ids, attention_mask, training=False, compute_grads=False, dec_ids=dec_ids, dec_mask=dec_mask,
