@@ -273,7 +273,11 @@ int kvq_gelu_bwd_bias(const void* h, const void* g_a, void* g_h, int64_t N, int6
 
 /* BertSelfAttention / BertCrossAttention core (:111-204) for S_q, S_k <= 32 (bf16 with 16-byte aligned rows: <= 128, in 32-token
  * blocks) and head dim 64: softmax(q k^T * scale + mask) v with dropout on the probabilities.  q [B*Sq, ldq], k/v [B*Sk, ldk/ldv], out [B*Sq, ldo]; head h lives at columns h*64..;
- * mask [B,Sk] int64 (1 = attend) or NULL; causal != 0 adds key <= query.  lse [B,nh,Sq] (may be NULL). */
+ * mask [B,Sk] int64 (1 = attend) or NULL; causal != 0 adds key <= query.  lse [B,nh,Sq] (may be NULL).
+ * A query row without any attended key (a mask row of zeros; under causal, a sentence whose first attended key lies behind the
+ * query) has all-zero probabilities: its output row is exactly 0, its lse is log(1e-37), and in the backward it contributes
+ * exactly 0 to g_q, g_k, g_v and the bias partials -- never NaN.  (HuggingFace's additive finfo.min mask gives uniform attention
+ * over the padding there: a caller that needs that behaviour must not pass an all-zero mask row.) */
 int kvq_attn_fwd(const void* q, const void* k, const void* v, const int64_t* mask, int B, int nh, int Sq, int Sk, int dh,
                  int ldq, int ldk, int ldv, int ldo, int causal, float scale, float p_drop, uint64_t seed, uint32_t site,
                  int io_dtype, void* out, float* lse, void* stream);

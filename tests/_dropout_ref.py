@@ -77,6 +77,31 @@ def site_keys(n_enc, n_dec):
     return keys
 
 
+def attend_allowed(B, Sq, Sk, key_mask, causal, device):
+    """[B, 1, Sq, Sk] bool: which (query, key) pairs attend -- key_mask [B, Sk] (1 = attend) or None, causal = key <= query."""
+    allow = torch.ones(B, 1, Sq, Sk, dtype=torch.bool, device=device)
+    if key_mask is not None:
+        allow = allow & key_mask.bool().to(device)[:, None, None, :]
+    if causal:
+        allow = allow & torch.ones(Sq, Sk, dtype=torch.bool, device=device).tril()[None, None]
+    return allow
+
+
+def masked_softmax(s, allow, empty_rows_zero=False):
+    """softmax over the keys of scaled scores s with the additive mask of BertSelfAttention (-inf where a pair does not attend).
+    A query row without any attended key is NaN in torch; empty_rows_zero defines it as all-zero probabilities (and a zero
+    gradient), which is what the HIP kernels compute there (include/kvq.h, kvq_attn_fwd)."""
+    if not empty_rows_zero:
+        return torch.softmax(s.masked_fill(~allow, float("-inf")), -1)
+    some = allow.any(-1, keepdim=True)
+    return torch.softmax(s.masked_fill(~allow & some, float("-inf")), -1) * some.to(s.dtype)
+
+
+def dropout_scale(x, keep, p):
+    """x * keep / (1 - p): `keep` a 0 / 1 tensor of x's shape."""
+    return x * (keep.to(device=x.device, dtype=x.dtype) / (1.0 - p))
+
+
 def ref_step(W, ids, mask, nh, eps=1e-12, dec_ids=None, dec_mask=None, target=None, idx=None, beta=0.25, keep=None,
              p_hid=0.0, p_attn=0.0, pad_idx=0, dtype=torch.float64):
     """One step of the model whose parameters are W {engine name: tensor} (any device / dtype; upcast to `dtype`).
@@ -99,7 +124,7 @@ def ref_step(W, ids, mask, nh, eps=1e-12, dec_ids=None, dec_mask=None, target=No
         if k is None:
             return x
         assert tuple(k.shape) == tuple(x.shape), (key, tuple(k.shape), tuple(x.shape))
-        return x * (k.to(device=x.device, dtype=x.dtype) / (1.0 - p))
+        return dropout_scale(x, k, p)
 
     def ln(x, pre):
         return F.layer_norm(x, (H,), P[pre + ".w"], P[pre + ".b"], eps)
@@ -115,12 +140,7 @@ def ref_step(W, ids, mask, nh, eps=1e-12, dec_ids=None, dec_mask=None, target=No
         k = F.linear(src, P[pre + "k.w"], P[pre + "k.b"]).view(B, Sk, nh, dh).transpose(1, 2)
         v = F.linear(src, P[pre + "v.w"], P[pre + "v.b"]).view(B, Sk, nh, dh).transpose(1, 2)
         s = q @ k.transpose(-1, -2) / math.sqrt(dh)
-        allow = torch.ones(B, 1, Sq, Sk, dtype=torch.bool, device=x.device)
-        if key_mask is not None:
-            allow = allow & key_mask.bool().to(x.device)[:, None, None, :]
-        if causal:
-            allow = allow & torch.ones(Sq, Sk, dtype=torch.bool, device=x.device).tril()[None, None]
-        pr = drop(torch.softmax(s.masked_fill(~allow, float("-inf")), -1), key, p_attn)
+        pr = drop(masked_softmax(s, attend_allowed(B, Sq, Sk, key_mask, causal, x.device)), key, p_attn)
         return (pr @ v).transpose(1, 2).reshape(B * Sq, H)
 
     def out_block(pre, wname, h, resid, key, lnname):

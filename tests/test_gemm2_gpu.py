@@ -55,11 +55,14 @@ def test_gemm_bias_accumulate_strides(layout):
     big = torch.randn((M, N + 40), device="cuda").to(torch.bfloat16)
     out = big[:, 8:8 + N]                                      # row stride N + 40, offset 16 bytes
     before = out.float().clone()
+    snapshot = big.clone()
     nnops.gemm(a, b, layout, bias=bias, out=out, accumulate=True)
     want = (ref + bias.float()).to(torch.bfloat16).float() + before          # kernel rounds the product, then adds C in f32
     err = (out.float() - want).abs().max().item()
     assert err <= 2.0 ** -7 * want.abs().max().item(), err
-    assert torch.equal(big[:, :8], big[:, :8]) and torch.isfinite(big.float()).all()
+    bits = lambda t: t.contiguous().view(torch.int16)
+    assert torch.equal(bits(big[:, :8]), bits(snapshot[:, :8])) and torch.equal(bits(big[:, 8 + N:]), bits(snapshot[:, 8 + N:]))
+    assert torch.isfinite(big.float()).all()
 
 
 def test_gemm_does_not_touch_memory_outside_the_output():
