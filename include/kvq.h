@@ -297,6 +297,28 @@ int kvq_attn_bwd_saved(const void* q, const void* k, const void* v, const int64_
  * 0 .. nh*64 -- the partial rows of the q/k/v projection bias gradients (modeling_bert.py:83-85 biases), to be finished by
  * kvq_reduce_batch over the B rows.  The MFMA kernels emit them on the way out; the other flavours run a column-sum pass. */
 
+/* The attention PROBABILITIES of the same operands (one layer's `attentions` / `cross_attentions` of HuggingFace's
+ * output_attentions=True, modeling_bert.py:139-204), without dropout -- an evaluation quantity: launches of their own, the forward
+ * kernels are untouched.  q / k / mask / causal / scale / io_dtype as in kvq_attn_fwd; v is part of the operand description and is
+ * not read.  Either or both of
+ *   probs [B, nh, Sq, Sk] f32   the per-sentence probabilities: the UNROUNDED f32 softmax of the f32 score accumulation (what the
+ *                               forward kernels hold before they round P to bf16 for P.V);
+ *   table [nh, Sq, Sk]   f64    table += sum over the B sentences of this call (the mean over everything seen is table / count,
+ *                               taken by the caller at the end).
+ * A query row without any attended key has all-zero probabilities, as in kvq_attn_fwd, and still counts as a sentence.
+ * Deterministic, no floating-point atomics: a workgroup owns a contiguous run of sentences of one head, sums them in ascending
+ * order in f64 registers and leaves one slab in `ws`; a second kernel adds the slabs in ascending order into `table`.  Two calls on
+ * the same inputs give the same bits.  ws: kvq_attn_probs_workspace_bytes(B, nh, Sq, Sk) bytes, 16-byte aligned, needed only with a
+ * table.  Kernels only (no memset / memcpy nodes): capturable.
+ * Flavours: bf16 with 16-byte aligned rows and Sq, Sk <= 32: scores on v_mfma_f32_32x32x16_bf16; f32 (and unaligned bf16) <= 32: the
+ * LDS-tile kernel; bf16 with 33..128 tokens on either side: REQUIRES lse [B, nh, Sq] of kvq_attn_fwd on the same operands
+ * (P = exp(s - lse) per 32-key block, then each row is normalised by its own sum, which removes lse's rounding); at <= 32
+ * tokens lse is ignored and may be NULL.  Whatever kvq_attn_fwd refuses is refused here with the same status. */
+size_t kvq_attn_probs_workspace_bytes(int B, int nh, int Sq, int Sk);
+int kvq_attn_probs(const void* q, const void* k, const void* v, const int64_t* mask, const float* lse, int B, int nh, int Sq, int Sk,
+                   int dh, int ldq, int ldk, int ldv, int causal, float scale, int io_dtype, float* probs, double* table, void* ws,
+                   size_t ws_bytes, void* stream);
+
 /* bf16 attention flavour: 2 (default) = MFMA kernels (v_mfma_f32_32x32x16_bf16 for all five products), 1 = packed-dot
  * kernels (v_dot2c_f32_bf16); both round probabilities / dS to bf16 before P.V, dS.K, dS^T.Q, P^T.dO.  0 = convert-and-fma
  * kernels (f32 probabilities).  All flavours draw the same dropout mask.  f32 io always uses the f32 kernels.  The selection is

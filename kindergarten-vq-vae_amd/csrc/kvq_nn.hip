@@ -2434,6 +2434,190 @@ __global__ __launch_bounds__(64) void attn_bwd_blk_dkv_kernel(AttnParams p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Attention-map census (kvq_attn_probs): the probabilities themselves, per sentence and / or summed over sentences.
+//   The forward kernels above keep P in registers and hand out only P.V; these kernels stop after the softmax, with the same
+//   loads, score products and scores_to_probs() / blk_scores(), and without dropout.
+//   One wave = one workgroup owns head hd and the sentences [run * R, min(B, run * R + R)): it walks them in ascending order,
+//   stores each sentence's P (optional) and adds it to 16 f64 registers per lane (f32 values added in f64: the sum of a run is
+//   exact to ~1e-16 whatever its length), then leaves the run's [Sq][Sk] f64 slab.  probs_slabs_kernel adds the slabs of a head in
+//   ascending run order into the caller's table.  No atomics anywhere: the bits do not depend on scheduling.
+//   R (attn_probs_run_len): max(8, ceil(B nh / 1024)), measured (profiles/attention_maps.md section 3).  The second term keeps
+//   256 CUs x 4 SIMDs covered by one wave each at large B; the floor is what the slab pass dictates: it reads one slab per run,
+//   and at the benchmark shape (B 256, nh 12) runs of 8 (32 runs per head, 384 workgroups) take 24 us per call against 33 for runs
+//   of 3 (1032 workgroups), 43 for runs of 2 and 76 for runs of 1 -- a second wave per SIMD buys less than its slab costs.
+// ---------------------------------------------------------------------------------------------------------------
+struct ProbsOut {
+    float* probs;     // [B, nh, Sq, Sk] or null
+    double* slab;     // [runs, nh, Sq, Sk] or null
+    int run_len;
+    int vec;          // Sk % 4 == 0 and 16-byte aligned outputs: a lane's four neighbouring keys leave as one piece
+};
+
+// the lane's 16 values x of one row (keys attn_key<LAY>(h, jj), in aligned groups of four) -> row[0 .. nkeys)
+template <int LAY, typename T>
+__device__ __forceinline__ void store_row16(T* row, int nkeys, int vec, int h, const T (&x)[16]) {
+    struct alignas(16) V4 { T a, b, c, d; };
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int j = attn_key<LAY>(h, 4 * c);
+        if (vec) {
+            if (j < nkeys) *reinterpret_cast<V4*>(row + j) = V4{x[4 * c], x[4 * c + 1], x[4 * c + 2], x[4 * c + 3]};
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (j + t < nkeys) row[j + t] = x[4 * c + t];
+        }
+    }
+}
+// one sentence's probabilities of the lane's row: out to probs (prow: the row's first key of this block, null = not wanted / no such
+// row) and into the run's sums
+template <int LAY>
+__device__ __forceinline__ void probs_emit(float* prow, int nkeys, int vec, int h, const float (&s)[16], double (&acc)[16]) {
+#pragma unroll
+    for (int jj = 0; jj < 16; ++jj) acc[jj] += (double)s[jj];
+    if (prow) store_row16<LAY, float>(prow, nkeys, vec, h, s);
+}
+__device__ __forceinline__ void probs_run(const AttnParams& p, const ProbsOut& o, int run, int& b0, int& b1) {
+    b0 = run * o.run_len;
+    b1 = b0 + o.run_len < p.B ? b0 + o.run_len : p.B;
+}
+
+// bf16, <= 32 tokens: the loads, the LDS row image and the score MFMAs of attn_fwd_mfma_kernel<true, *>
+__global__ __launch_bounds__(64) void attn_probs_mfma_kernel(AttnParams p, ProbsOut o) {
+    __shared__ __attribute__((aligned(16))) unsigned Vt[16 * AM_LDT];
+    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+    const int hd = blockIdx.x % p.nh, run = blockIdx.x / p.nh;
+    const bool qvalid = r < p.Sq;
+    int b0, b1;
+    probs_run(p, o, run, b0, b1);
+    double acc[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = 0.0;
+    for (int b = b0; b < b1; ++b) {
+        const int64_t mv = attn_mask_element(p, b);
+        uint4 kf[4], qf[4], gk[4], gq[4];
+        load_rows_coalesced(p.k, (size_t)b * p.Sk * p.ldk + hd * AT_D, p.ldk, p.Sk, lane, gk);
+        load_rows_coalesced(p.q, (size_t)b * p.Sq * p.ldq + hd * AT_D, p.ldq, p.Sq, lane, gq);
+        const unsigned long long kmask = attn_mask_ballot(p, mv);
+        rows_to_chunks(Vt, r, h, lane, gk, kf);
+        rows_to_chunks(Vt, r, h, lane, gq, qf);
+        f32x16 sc = zero16();
+#pragma unroll
+        for (int s = 0; s < 4; ++s) sc = mfma32(kf[s], qf[s], sc);      // S^T[key][query]
+        float s[16];
+#pragma unroll
+        for (int v = 0; v < 16; ++v) s[v] = sc[v];
+        float lse;
+        scores_to_probs<1>(p, b, r, h, qvalid, s, lse, &kmask);
+        probs_emit<1>(o.probs && qvalid ? o.probs + (((size_t)b * p.nh + hd) * p.Sq + r) * p.Sk : nullptr, p.Sk, o.vec, h, s, acc);
+    }
+    if (o.slab && qvalid) store_row16<1, double>(o.slab + (((size_t)run * p.nh + hd) * p.Sq + r) * p.Sk, p.Sk, o.vec, h, acc);
+}
+
+// f32 io (and bf16 rows that are not 16-byte aligned), <= 32 tokens: the LDS tiles and dot products of attn_fwd_kernel
+template <int DT>
+__global__ __launch_bounds__(64) void attn_probs_kernel(AttnParams p, ProbsOut o) {
+    typedef typename Lds<DT>::T T;
+    __shared__ __attribute__((aligned(16))) T Ks[AT_S * AT_D];
+    __shared__ __attribute__((aligned(16))) T Qs[AT_S * AT_QLD];
+    const int lane = threadIdx.x, i = lane & 31, h = lane >> 5;
+    const int hd = blockIdx.x % p.nh, run = blockIdx.x / p.nh;
+    const bool kvalid = i < p.Sk, qvalid = i < p.Sq;
+    const int ik = kvalid ? i : p.Sk - 1, iq = qvalid ? i : p.Sq - 1;
+    int b0, b1;
+    probs_run(p, o, run, b0, b1);
+    double acc[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = 0.0;
+    for (int b = b0; b < b1; ++b) {
+        __syncthreads();                                                  // the previous sentence's reads of the tiles are done
+        stage_row<DT>(p.k, ((size_t)b * p.Sk + ik) * p.ldk + hd * AT_D + 32 * h, kvalid, Ks + i * AT_D + 32 * h);
+        stage_row<DT>(p.q, ((size_t)b * p.Sq + iq) * p.ldq + hd * AT_D + 32 * h, qvalid, Qs + i * AT_QLD + 32 * h);
+        __syncthreads();
+        float s[16];
+#pragma unroll
+        for (int jj = 0; jj < 16; ++jj) s[jj] = 0.f;
+        rows_dot16<T>(Qs + i * AT_QLD, Ks, AT_D, h, s);
+        float lse;
+        scores_to_probs(p, b, i, h, qvalid, s, lse);
+        probs_emit<0>(o.probs && qvalid ? o.probs + (((size_t)b * p.nh + hd) * p.Sq + i) * p.Sk : nullptr, p.Sk, o.vec, h, s, acc);
+    }
+    if (o.slab && qvalid) store_row16<0, double>(o.slab + (((size_t)run * p.nh + hd) * p.Sq + i) * p.Sk, p.Sk, o.vec, h, acc);
+}
+
+// bf16, 33 .. 128 tokens: one wave per (run, head, query block).  exp(s - lse) of every 32-key block as blk_grad_pair() forms it
+// (the forward's lse keeps the exponent in range); the four blocks stay in registers and the row is divided by its own sum, so
+// that lse's rounding (half an ulp of a number near 5, 2^-22, on EVERY element of the row) does not reach the result.
+__global__ __launch_bounds__(64) void attn_probs_blk_kernel(AttnParams p, ProbsOut o) {
+    constexpr int NKB = AT_SMAX / 32;
+    const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
+    const int nqb = (p.Sq + 31) / 32, nkb = (p.Sk + 31) / 32;
+    const int qb = blockIdx.x % nqb, hd = (blockIdx.x / nqb) % p.nh, run = blockIdx.x / (nqb * p.nh);
+    const int ig = 32 * qb + r;
+    const bool qvalid = ig < p.Sq;
+    const int rq = qvalid ? ig : p.Sq - 1;
+    int b0, b1;
+    probs_run(p, o, run, b0, b1);
+    double acc[NKB][16];
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[kb][v] = 0.0;
+    for (int b = b0; b < b1; ++b) {
+        uint4 qf[4];
+        load_row_chunks(p.q, ((size_t)b * p.Sq + rq) * p.ldq + hd * AT_D, h, qvalid, qf);
+        const float lse = p.lse[((size_t)b * p.nh + hd) * p.Sq + rq];
+        float e[NKB][16];
+        float sum = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) {
+            if (kb < nkb) {                                               // (uniform)
+                const int k0 = 32 * kb, kg = k0 + r;
+                const bool kvalid = kg < p.Sk;
+                uint4 kf[4];
+                load_row_chunks(p.k, ((size_t)b * p.Sk + (kvalid ? kg : p.Sk - 1)) * p.ldk + hd * AT_D, h, kvalid, kf);
+                const unsigned kmask = blk_key_mask(p, b, k0);
+                f32x16 sc = zero16();
+#pragma unroll
+                for (int s = 0; s < 4; ++s) sc = mfma32(kf[s], qf[s], sc);      // S^T[key][query]
+#pragma unroll
+                for (int v = 0; v < 16; ++v) e[kb][v] = sc[v];
+                blk_scores(p, kmask, ig, k0, h, qvalid, e[kb]);
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    e[kb][v] = __expf(e[kb][v] - lse);                          // exp(-inf) = 0 where the pair does not attend
+                    sum += e[kb][v];
+                }
+            }
+        }
+        sum += __shfl_xor(sum, 32, WAVE);
+        const float inv = sum > 0.f ? 1.0f / sum : 0.f;
+#pragma unroll
+        for (int kb = 0; kb < NKB; ++kb) {
+            if (kb < nkb) {
+#pragma unroll
+                for (int v = 0; v < 16; ++v) e[kb][v] *= inv;
+                probs_emit<1>(o.probs && qvalid ? o.probs + (((size_t)b * p.nh + hd) * p.Sq + ig) * p.Sk + 32 * kb : nullptr,
+                              p.Sk - 32 * kb, o.vec, h, e[kb], acc[kb]);
+            }
+        }
+    }
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+        if (kb < nkb && o.slab && qvalid)
+            store_row16<1, double>(o.slab + (((size_t)run * p.nh + hd) * p.Sq + ig) * p.Sk + 32 * kb, p.Sk - 32 * kb, o.vec, h, acc[kb]);
+}
+
+// table[e] += (slab[0][e] + slab[1][e] + ...) in that order, e < n = nh * Sq * Sk
+__global__ __launch_bounds__(256) void probs_slabs_kernel(const double* __restrict__ slab, int runs, long long n, double* __restrict__ table) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    double t = 0.0;
+    for (int s = 0; s < runs; ++s) t += slab[(size_t)s * n + e];
+    table[e] += t;
+}
+
 // Zero up to four byte ranges (16-byte aligned, multiples of 16 bytes) in ONE launch: the gradient tables of BertEmbeddings
 // (word / position / token-type) before the embedding-gradient kernels add into them -- three fill launches per table set before.
 struct ZeroRanges {
@@ -2994,6 +3178,58 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, const int6
     else if (al && g_attn_variant == 1) hipLaunchKernelGGL(attn_fwd_bf16_kernel, dim3((unsigned)(B * nh)), dim3(64), 0, st, p);
     else hipLaunchKernelGGL(attn_fwd_kernel<KVQ_BF16>, dim3((unsigned)(B * nh)), dim3(64), 0, st, p);
     return check_launch("attn_fwd_kernel");
+}
+
+// sentences per workgroup of the probability kernels: the rule is written down beside them.  KVQ_ATTN_PROBS_RUN=<n> (read once): A/B
+// switch that forces the run length (tools/attention_maps_cost.py measures the rule against its neighbours with it)
+static int attn_probs_run_len(int B, int nh) {
+    static const int forced = [] { const char* e = getenv("KVQ_ATTN_PROBS_RUN"); return e ? atoi(e) : 0; }();
+    if (forced > 0) return forced;
+    const long long r = ((long long)B * nh + 1023) / 1024;
+    return r < 8 ? 8 : (int)r;
+}
+
+size_t kvq_attn_probs_workspace_bytes(int B, int nh, int Sq, int Sk) {
+    if (B <= 0 || nh <= 0 || Sq <= 0 || Sk <= 0) return 0;
+    const int R = attn_probs_run_len(B, nh);
+    const size_t runs = (size_t)((B + R - 1) / R);
+    return ((runs * nh * Sq * Sk * sizeof(double)) + 255) / 256 * 256;
+}
+
+int kvq_attn_probs(const void* q, const void* k, const void* v, const int64_t* mask, const float* lse, int B, int nh, int Sq, int Sk,
+                   int dh, int ldq, int ldk, int ldv, int causal, float scale, int io_dtype, float* probs, double* table, void* ws,
+                   size_t ws_bytes, void* stream) {
+    (void)v; (void)ldv;                                                   // part of the operand description; the probabilities do not read V
+    KVQ_REQUIRE(q && k, "kvq_attn_probs: null pointer argument");
+    KVQ_REQUIRE(probs || table, "kvq_attn_probs: neither probs nor table asked for");
+    int rc = attn_check(B, nh, Sq, Sk, dh, io_dtype);
+    if (rc) return rc;
+    KVQ_REQUIRE(!table || (ws && ws_bytes >= kvq_attn_probs_workspace_bytes(B, nh, Sq, Sk) && (uintptr_t)ws % 16 == 0),
+                "kvq_attn_probs: the table needs a 16-byte aligned workspace of kvq_attn_probs_workspace_bytes(B, nh, Sq, Sk) bytes");
+    AttnParams p = {};
+    p.q = q; p.k = k; p.mask = mask; p.lse = const_cast<float*>(lse);
+    p.B = B; p.nh = nh; p.Sq = Sq; p.Sk = Sk; p.ldq = ldq; p.ldk = ldk; p.causal = causal; p.scale = scale;
+    ProbsOut o = {};
+    o.probs = probs; o.slab = table ? (double*)ws : nullptr;
+    o.run_len = attn_probs_run_len(B, nh);
+    o.vec = Sk % 4 == 0 && (uintptr_t)probs % 16 == 0 ? 1 : 0;
+    const int runs = (B + o.run_len - 1) / o.run_len;
+    hipStream_t st = (hipStream_t)stream;
+    const bool al = (ldq % 8 == 0) && (ldk % 8 == 0) && (((uintptr_t)q | (uintptr_t)k) % 16 == 0);
+    if (attn_long(Sq, Sk)) {
+        KVQ_REQUIRE(lse, "kvq_attn_probs: sequences above %d tokens need the forward's log-sum-exp", AT_S);
+        KVQ_REQUIRE(al, "kvq_attn_probs: sequences above %d tokens need 16-byte aligned rows", AT_S);
+        KVQ_REQUIRE(!causal || Sq == Sk, "kvq_attn_probs: causal attention needs Sq == Sk");
+        hipLaunchKernelGGL(attn_probs_blk_kernel, dim3((unsigned)(runs * nh * ((Sq + 31) / 32))), dim3(64), 0, st, p, o);
+    }
+    else if (io_dtype == KVQ_BF16 && al) hipLaunchKernelGGL(attn_probs_mfma_kernel, dim3((unsigned)(runs * nh)), dim3(64), 0, st, p, o);
+    else if (io_dtype == KVQ_BF16) hipLaunchKernelGGL(attn_probs_kernel<KVQ_BF16>, dim3((unsigned)(runs * nh)), dim3(64), 0, st, p, o);
+    else hipLaunchKernelGGL(attn_probs_kernel<KVQ_F32>, dim3((unsigned)(runs * nh)), dim3(64), 0, st, p, o);
+    rc = check_launch("attn_probs_kernel");
+    if (rc || !table) return rc;
+    const long long n = (long long)nh * Sq * Sk;
+    hipLaunchKernelGGL(probs_slabs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double*)ws, runs, n, table);
+    return check_launch("probs_slabs_kernel");
 }
 
 // per-batch column sums of a [B*S, ld] gradient (head columns 0 .. nh*64): the fallback of the kernels that do not emit them

@@ -1,4 +1,5 @@
-"""Word x code census of the quantiser's indices -- host side of `kvq_code_census` (include/kvq.h).
+"""Device-resident census tables: the word x code census of the quantiser's indices (host side of `kvq_code_census`,
+include/kvq.h) and, at the end of the file, the attention-map census (`AttentionCensus`, host side of `kvq_attn_probs`).
 
 Boundary mirrored: the bookkeeping of analyses/unsupervised_vq_disentanglement/unsupervised_vq_disentanglement.py:156-235.
 The reference walks sentence -> word -> token in Python, tokenising every word of every sentence again to learn how many
@@ -117,3 +118,45 @@ class CodeCensus:
             histograms[w] = {k: int(row[k]) for k in range(self.K)}
         words_of_code = {k: sorted(words[i] for i in torch.nonzero(a[:, k]).flatten().tolist()) for k in range(self.K)}
         return {"populated": populated, "histograms": histograms, "words_of_code": words_of_code}
+
+
+ATTENTION_FAMILIES = ("enc_self", "dec_self", "cross")
+
+
+class AttentionCensus:
+    """Mean attention maps over everything seen, one f64 table [L, nh, queries, keys] per family on the device -- the content of
+    analyses/cross_attention/extract_model_cross_attention.py's `*_mean_across_batch_size.pth` (:103-108), without its host
+    copies of every batch (:85-86: "had to limit to 69 batches in order to avoid memory crashes").
+    Sq / Sk: the decoder's / the encoder's padded length.  "dec_self" is [L, nh, Sq, Sq], "cross" [L, nh, Sq, Sk], "enc_self"
+    [L, nh, Sk, Sk].  TrainEngine.attention_maps(..., census=self) adds each batch's sum over sentences (kvq_attn_probs: f64,
+    no atomics, the same bits on every run) and the sentence count; results() reads the tables back once."""
+
+    def __init__(self, n_layers: int, n_heads: int, Sq: int, Sk: int, families=("dec_self", "cross"), device=None):
+        if n_layers < 1 or n_heads < 1 or Sq < 1 or Sk < 1:
+            raise KvqError("AttentionCensus: n_layers, n_heads, Sq, Sk >= 1")
+        if max(Sq, Sk) > 128:
+            raise KvqError("AttentionCensus: the attention kernels end at 128 tokens")
+        families = tuple(families)
+        if not families or any(f not in ATTENTION_FAMILIES for f in families) or len(set(families)) != len(families):
+            raise KvqError(f"AttentionCensus: families must be distinct names out of {ATTENTION_FAMILIES}, got {families}")
+        self.L, self.nh, self.Sq, self.Sk, self.families = int(n_layers), int(n_heads), int(Sq), int(Sk), families
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise KvqError("AttentionCensus: the tables live on the GPU (no CPU path)")
+        dims = {"enc_self": (self.Sk, self.Sk), "dec_self": (self.Sq, self.Sq), "cross": (self.Sq, self.Sk)}
+        self.tables = {f: torch.zeros((self.L, self.nh) + dims[f], dtype=torch.float64, device=self.device) for f in families}
+        self.count = 0                        # sentences seen
+
+    def require(self, family, n_layers, n_heads, n_queries, n_keys, device) -> None:
+        """Raises unless the table of `family` is [n_layers, n_heads, n_queries, n_keys] on `device`."""
+        t = self.tables.get(family)
+        want = (n_layers, n_heads, n_queries, n_keys)
+        if t is None or tuple(t.shape) != want or t.device != torch.device(device):
+            raise KvqError(f"AttentionCensus: the {family!r} table is {None if t is None else tuple(t.shape)} on {self.device}; "
+                           f"this model and batch need {want} on {device}")
+
+    def results(self) -> Dict[str, torch.Tensor]:
+        """{family: float32 [L, nh, queries, keys]} on the host: table / sentences seen."""
+        if self.count < 1:
+            raise KvqError("AttentionCensus.results: no sentence was added")
+        return {f: (t.cpu() / self.count).to(torch.float32) for f, t in self.tables.items()}

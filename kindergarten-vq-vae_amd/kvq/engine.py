@@ -403,6 +403,7 @@ class TrainEngine:
         self._step_host = 0
         self._step_seed = (self.seed * 1000003) & 0x7FFFFFFFFFFFFFF      # + step count on the device
         self._graphs, self._eager_seen, self._cap, self._prepared = {}, {}, None, None
+        self._maps = None                  # attention_maps() only: where _attn_block_fwd leaves the probabilities
         self._own_fwd = os.environ.get("KVQ_OWN_GEMM", "1") != "0"
         self._gumbel_own = 0                  # products of the Gumbel mode that ran on the own GEMM (tests read it)
         if os.environ.get("KVQ_GEMM_TILE"):       # "NxK:tile;NxK:tile" (A/B runs on the GPU box)
@@ -1006,6 +1007,8 @@ class TrainEngine:
             self._x8[(ctx.data_ptr(), pre + "o.w")] = ctx8
         else:
             ctx, lse = nnops.attn_fwd(q, k, v, mask, B, nh, Sq, Sk, causal, p_attn, self._step_seed, site_a)
+        if self._maps is not None:
+            self._maps_emit(pre, q, k, v, mask, causal, B, Sq, Sk, lse)
         out, lnpre, mean, rstd = self._dense_residual_ln(ctx, pre + "o.w", pre + "o.b", x, pre + "ln.w", pre + "ln.b", cfg.layer_norm_eps,
                                                          p_hid, site_o, next_key=next_key)
         # (lse: only the kernels above 32 tokens work from the saved log-sum-exp)
@@ -1253,6 +1256,61 @@ class TrainEngine:
             self._E_version = None
         return self.forward_backward(enc_ids, enc_mask, training=False, compute_grads=False, quantizer_training=quantizer_training,
                                      stop_after_quantizer=True)
+
+    _MAP_FAMILY = {("enc", "sa"): "enc_self", ("dec", "sa"): "dec_self", ("dec", "ca"): "cross"}
+
+    def _maps_emit(self, pre, q, k, v, mask, causal, B, Sq, Sk, lse):
+        """attention_maps(): the probabilities of the attention block `pre` ("dec.1.ca."), from launches of their own on the
+        block's q / k views and mask -- into the census' table of (family, layer) and / or the per-sentence stack."""
+        side, layer, kind = pre.split(".")[:3]
+        family = self._MAP_FAMILY[(side, kind)]
+        m = self._maps
+        if family not in m["families"]:
+            return
+        layer = int(layer)
+        probs = m["per_sentence"][family][layer] if m["per_sentence"] is not None else None
+        table = m["census"].tables[family][layer] if m["census"] is not None else None
+        nnops.attn_probs(q, k, v, mask, B, self.nh, Sq, Sk, causal, lse=lse if max(Sq, Sk) > 32 else None, probs=probs, table=table)
+
+    def attention_maps(self, enc_ids, enc_mask, dec_ids=None, dec_mask=None, census=None, per_sentence=False):
+        """The attention probabilities of an evaluation forward (no dropout, quantiser in eval mode, eager; the schedule of
+        forward_logits) -- what HuggingFace returns as `attentions` / `cross_attentions` under output_attentions=True, which
+        analyses/cross_attention/extract_model_cross_attention.py:79-86 stacks and averages on the host.  Families: "dec_self"
+        (causal, decoder mask), "cross" (no key mask: models/bagon/Bagon.py:50-53 passes none), "enc_self"; those of `census`, or
+        the decoder's two without one.
+        census: a kvq.census.AttentionCensus -- every asked-for block adds the sum over this batch's sentences into its f64 table
+        on the device; nothing of size B is kept.  per_sentence: also return {family: f32 [L, B, nh, Sq, Sk]}, i.e.
+        torch.stack(decoder_output.cross_attentions) etc.  The maps come from kernels of their own (kvq_attn_probs) after each
+        block's forward kernel: the training step and forward_logits launch exactly what they launched before."""
+        if census is None and not per_sentence:
+            raise KvqError("TrainEngine.attention_maps: pass a census, per_sentence=True, or both")
+        if self._cap is not None or torch.cuda.is_current_stream_capturing():
+            raise KvqError("TrainEngine.attention_maps is an eager call: not under graph capture")
+        if self.group is not None or self._dp:
+            raise KvqError("TrainEngine.attention_maps is a single-process call (this engine has a process group)")
+        families = tuple(census.families) if census is not None else ("dec_self", "cross")
+        B, Se = enc_ids.shape
+        Sd = Se if dec_ids is None else dec_ids.shape[1]
+        dims = {"enc_self": (self.n_enc_layers, Se, Se), "dec_self": (self.n_dec_layers, Sd, Sd), "cross": (self.n_dec_layers, Sd, Se)}
+        if census is not None:
+            for f in families:             # before anything is launched: a table that does not fit must not leave half a batch behind
+                census.require(f, dims[f][0], self.nh, dims[f][1], dims[f][2], self.dev)
+        stacks = None
+        if per_sentence:
+            stacks = {f: torch.empty((dims[f][0], B, self.nh, dims[f][1], dims[f][2]), dtype=torch.float32, device=self.dev)
+                      for f in families}
+        self.refresh_if_params_changed()
+        if getattr(self, "_epack", None) is not None:
+            self._E_version = None
+        self._maps = dict(families=families, census=census, per_sentence=stacks)
+        try:
+            self.forward_backward(enc_ids, enc_mask, training=False, compute_grads=False, dec_ids=dec_ids, dec_mask=dec_mask,
+                                  quantizer_training=False)
+        finally:
+            self._maps = None
+        if census is not None:
+            census.count += B
+        return stacks
 
     def _forward_backward(self, input_ids, attention_mask, training, compute_grads, dec_ids=None, dec_mask=None, want_logits=False,
                           defer=False, target_ids=None):

@@ -189,6 +189,27 @@ def attn_fwd(q, k, v, mask, B, nh, Sq, Sk, causal, p_drop=0.0, seed=0, site=0, o
     return ctx, lse
 
 
+def attn_probs(q, k, v, mask, B, nh, Sq, Sk, causal, lse=None, probs=None, table=None):
+    """The softmax probabilities of attn_fwd's operands, without dropout (kvq_attn_probs): written to probs [B, nh, Sq, Sk] f32
+    and / or summed over the B sentences INTO table [nh, Sq, Sk] f64 (contiguous, or a contiguous slice).  lse: attn_fwd's, needed
+    above 32 tokens.  Returns probs."""
+    require_gpu(q, k)
+    for t, dt, shape in ((probs, torch.float32, (B, nh, Sq, Sk)), (table, torch.float64, (nh, Sq, Sk))):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise KvqError(f"attn_probs: output must be a contiguous {dt} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    if lse is not None and (lse.dtype != torch.float32 or tuple(lse.shape) != (B, nh, Sq) or not lse.is_contiguous()):
+        raise KvqError("attn_probs: lse must be attn_fwd's contiguous f32 [B, nh, Sq]")
+    l = lib()
+    ws, nws = None, 0
+    if table is not None:
+        nws = l.kvq_attn_probs_workspace_bytes(B, nh, Sq, Sk)
+        ws = _workspace(q.device, nws)       # slabs: written and consumed inside this call, on this stream
+    check(l.kvq_attn_probs(q.data_ptr(), k.data_ptr(), _p(v), _p(mask), _p(lse), B, nh, Sq, Sk, 64, q.stride(0), k.stride(0),
+                           v.stride(0) if v is not None else 0, int(causal), 1.0 / 8.0, io_dtype_of(q), _p(probs), _p(table), _p(ws), nws,
+                           stream_ptr()), "kvq_attn_probs")
+    return probs
+
+
 def attn_fwd_fp8_ok(Sq, Sk):
     return bool(lib().kvq_attn_fwd_fp8_ok(int(Sq), int(Sk)))
 

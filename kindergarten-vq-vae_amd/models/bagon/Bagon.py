@@ -128,6 +128,20 @@ class Bagon(nn.Module):
         encoder_output = self.encode(encoder_input_ids, encoder_attention_mask)            # Bagon.py:46-48
         return self.decode(encoder_output, decoder_input_ids, decoder_attention_mask)      # Bagon.py:50-55
 
+    def attention_maps(self, encoder_input_ids, encoder_attention_mask, decoder_input_ids=None, decoder_attention_mask=None,
+                       census=None, per_sentence=False):
+        """The decoder's self- and cross-attention probabilities of an evaluation forward, on the engine's kernels
+        (TrainEngine.attention_maps): accumulated into a kvq.census.AttentionCensus and / or returned per sentence as
+        {family: [L, B, nh, Sq, Sk]} -- what analyses/cross_attention/extract_model_cross_attention.py:79-86 takes from
+        output_attentions=True.  There is no ATen path: the model must be on the GPU with shapes the engine serves."""
+        from kvq.engine import engine_of
+        if decoder_input_ids is None and decoder_attention_mask is None:
+            return engine_of(self).attention_maps(encoder_input_ids, encoder_attention_mask, census=census, per_sentence=per_sentence)
+        if decoder_input_ids is None:                      # a decoder mask of its own over the encoder's ids
+            decoder_input_ids = encoder_input_ids
+        return engine_of(self).attention_maps(encoder_input_ids, encoder_attention_mask, decoder_input_ids, decoder_attention_mask,
+                                              census=census, per_sentence=per_sentence)
+
     def forward_loss(self, encoder_input_ids, encoder_attention_mask, decoder_input_ids, decoder_attention_mask):
         """Fused step body of the plain autoencoder: (loss_recon, acc_per_batch, recon_ids) -- the loss block of
         models/bagon/Trainer.py:103-110 in one pass over the logits."""

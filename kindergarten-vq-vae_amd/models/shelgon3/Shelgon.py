@@ -78,6 +78,11 @@ class Shelgon(Bagon):
         with torch.no_grad():
             return self._quantize(self.encode(input_ids, attention_mask), device)[3]
 
+    def attention_maps(self, input_ids, attention_mask, census=None, per_sentence=False):
+        """Bagon.attention_maps for the autoencoding call (decoder input = encoder input, Shelgon.py:71), the cross-attention
+        reading the quantised encoder output."""
+        return super().attention_maps(input_ids, attention_mask, census=census, per_sentence=per_sentence)
+
     def forward_loss(self, input_ids, attention_mask):
         """Fused step body: (vq_loss, perplexity, indices, loss_recon, acc_per_batch, recon_ids)."""
         embeds = self.encode(input_ids, attention_mask)
