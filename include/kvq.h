@@ -502,6 +502,33 @@ int kvq_code_census(const int32_t* slot_first, const int64_t* idx, int64_t N, in
                     uint32_t* counts_first, uint32_t* n_bad, void* stream);
 
 
+/* ---- latent analyses: group means of encoder outputs, the shift along their difference, the codebook gather -------------------
+ * What analyses/latent_arithmetics/latent_arithmetics_Bagon.py:77-139 (v = mean enc(A) - mean enc(B); decode enc(C) + v) and
+ * analyses/latent_traversals/latent_traversals_Shelgon_latent_classes.py:113-161 (overwrite the discrete latent, decode) do on the
+ * host with every encoder output kept.  csrc/kvq_latent.hip.  Kernels only: capturable.  Activations are io_dtype (f32 / bf16)
+ * [B, S, H] with a row stride in ELEMENTS between consecutive (b, s) rows; 16-byte accesses where base and stride allow them.
+ *
+ * kvq_latent_group_sum: table [G, S, H] f64 += the sum of x[b] over the sentences b with group[b] == g, count [G] int64 += their
+ *   number.  group [B] int32: -1 = skip the sentence; a value >= G or < -1 is skipped and counted in *n_bad (optional).
+ *   Deterministic, no floating-point atomics: a workgroup owns a contiguous run of sentences and a span of (s, h), adds the run in
+ *   ascending sentence order in f64 registers and leaves a slab in ws; a second launch adds the slabs in ascending order into table.
+ *   The same inputs give the same bits.  ws: kvq_latent_group_sum_workspace_bytes(B, S, H, G), 16-byte aligned; table 16-byte aligned.
+ * kvq_latent_shift: out[b, s, :] = io(f32(x[b, s, :] + alpha * (table[g1, s, :] / count[g1] - table[g0, s, :] / count[g0]))) where
+ *   sel[b, s] != 0 (sel [B, S] int8, NULL = every position), the bits of x elsewhere.  f64 arithmetic, each operation rounded on
+ *   its own, then round-to-nearest-even to f32 and to io_dtype.  The counts are read on the device; a group with count 0 means
+ *   "no shift" (out = x).  out may be x.
+ * kvq_vq_lookup: out[n, g * Dg : (g + 1) * Dg] = io(E[g][idx[n][g]]) for idx [N, G] int64 and the f32 codebooks E [G, K, Dg] -- the
+ *   quantiser's gather without its distances: the codebook row itself, not the straight-through value fl(z + fl(e - z)).  An index
+ *   outside [0, K) leaves a zero row and is counted in *n_bad (optional). */
+size_t kvq_latent_group_sum_workspace_bytes(int64_t B, int S, int H, int G);
+int kvq_latent_group_sum(const void* x, int64_t ldx, const int32_t* group, int64_t B, int S, int H, int G, int io_dtype, double* table,
+                         int64_t* count, uint32_t* n_bad, void* ws, size_t ws_bytes, void* stream);
+int kvq_latent_shift(const void* x, int64_t ldx, const double* table, const int64_t* count, int g1, int g0, double alpha,
+                     const int8_t* sel, int64_t B, int S, int H, int G, int io_dtype, void* out, int64_t ldo, void* stream);
+int kvq_vq_lookup(const int64_t* idx, const float* E, int64_t N, int K, int Dg, int G, int io_dtype, void* out, int64_t ldo,
+                  uint32_t* n_bad, void* stream);
+
+
 /* Word-embedding gradient (autograd of the row gather of BertEmbeddings, modeling_bert.py:53-58):
  *     gW[id][:] (= | +=) sum over the tokens n with ids[n] == id of g[n][:],   tokens added in increasing n  (deterministic)
  * The caller passes the tokens sorted by id: sorted_ids[s] ascending and perm[s] = the token at sorted position s (a STABLE

@@ -1,0 +1,125 @@
+"""Traversal of the discrete latent -- counterpart of analyses/latent_traversals/latent_traversals_Shelgon_latent_classes.py.
+
+    PYTHONPATH=kindergarten-vq-vae_amd python3 kindergarten-vq-vae_amd/analyses/latent_traversals/code_traversal.py
+
+The reference (:66-161) takes the first OVERRIDE_TOT sentences with GENERATIVE_FACTOR == FACTOR_VALUE, encodes them, overwrites the
+discrete latent with a hand-written one, decodes with the encoder's ids and prints original against decoded sentence.  Its model
+is the latent-class Shelgon v1 (one-hot classes through proj_in / proj_out), which is not runnable upstream; the discrete latent
+of the Shelgon of models/shelgon3 is the code index per position, so the hand-written latent becomes: every code 0 .. K-1 at one
+position of the sentence (and one codebook, FACTOR_INDEX, of a MultiVectorQuantizer), all other positions as encoded.
+model.traverse_codes does this on the engine's kernels: encode once, K index rows, kvq_vq_lookup, decoder + LM head.
+Result file (the reference prints): <RESULTS_DIR>/code_traversal.feather (.csv when feather is unavailable) with one row per
+(sentence, position, code): input_sentence, position, code, own_code (bool), recon_sentence, n_changed_tokens.
+Without <RUN_DIR>/decoded_sentences_max_acc_only.* the sentences come from the dSentences corpus and its factor labels.
+Constants can be overridden from the environment as KVQ_<NAME>=<python literal>, as in models/shelgon3/config.py.
+"""
+import ast
+import os
+import sys
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))      # package root (common/, kvq/, models/, dsentences/, analyses/)
+
+import torch  # noqa: E402
+
+from analyses.get_max_acc_sentences import read_table, write_table  # noqa: E402
+from analyses.latent_arithmetics.latent_arithmetics import corpus_table  # noqa: E402
+from common.consts import *  # noqa: E402,F401,F403
+from kvq.tokenizer import load_tokenizer  # noqa: E402
+from models.shelgon3.MultiVectorQuantizer import MultiVectorQuantizer  # noqa: E402
+from models.shelgon3.Shelgon import Shelgon  # noqa: E402
+from models.shelgon3.VectorQuantizer import VectorQuantizer  # noqa: E402
+
+MODEL_NAME = "Shelgon"                                                                       # :25
+RUN_ID = "no_checkpoint"                                                                     # :27
+RUN_DIR = None                       # default: ./runs/<MODEL_NAME>/<RUN_ID> (:29)
+DECODED_SENTENCES_DF_PATH = None     # default: <RUN_DIR>/decoded_sentences_max_acc_only.feather (:31)
+GENERATIVE_FACTOR = "sentence_negation"                                                      # :68
+FACTOR_VALUE = "negative"                                                                    # :71
+OVERRIDE_TOT = 1                     # sentences taken from the head of the table (:85)
+POSITIONS = None                     # token positions to traverse; None = every non-padding position of the sentence
+FACTOR_INDEX = 0                     # which codebook of a MultiVectorQuantizer
+SENTENCES_PATH = "./data/dSentences/dSentences_sentences.npy"
+LATENT_CLASSES_LABELS_PATH = "./data/dSentences/dSentences_latent_classes_labels.npy"
+SYNTHETIC_SENTENCES = 65536
+TOKENIZED_SENTENCE_MAX_LENGTH = 12                                                           # run_conf (:103)
+TOKENIZER_ADD_SPECIAL_TOKENS = False                                                         # run_conf (:101)
+TOKENIZER_NAME = "bert-base-uncased"
+ENCODER_MODEL_NAME = "bert-base-uncased"
+DECODER_MODEL_NAME = "bert-base-uncased"
+COMPUTE_DTYPE = "bfloat16"
+VQ_MODE = "VectorQuantizer"          # or "MultiVectorQuantizer"
+VQ_N_E = 9
+VQ_E_DIM = 768
+VQ_BETA = 0.1
+VQ_N_FACTORS = 1
+CKPT_PATH = None                     # "<RUN_DIR>/Shelgon_ckpt_loss_recon_val_best.pth" (:55); None = fresh weights
+RESULTS_DIR = None                   # default: <RUN_DIR>
+
+for _k in [k for k in list(globals()) if k.isupper()]:
+    _v = os.environ.get("KVQ_" + _k)
+    if _v is not None:
+        try:
+            globals()[_k] = ast.literal_eval(_v)
+        except (ValueError, SyntaxError):
+            globals()[_k] = _v
+
+
+def code_traversal(model, tokenizer, sentences, device, seq_len, positions=None, factor=0, add_special_tokens=False):
+    """Rows of the result table for every (sentence, position, code)."""
+    t = tokenizer(list(sentences), return_tensors="pt", padding="max_length", max_length=seq_len, add_special_tokens=add_special_tokens)
+    ids, mask = t.input_ids.to(device), t.attention_mask.to(device)                          # :98-108
+    lengths = t.attention_mask.sum(1).tolist()
+    rows = []
+    for b, sentence in enumerate(sentences):
+        for pos in (positions if positions is not None else range(int(lengths[b]))):
+            out = model.traverse_codes(ids, mask, b, int(pos), factor=factor)                 # :139-150
+            decoded = tokenizer.batch_decode(out["recon_ids"].cpu())                         # :158-160
+            n_changed = out["changed"].sum(1).tolist()
+            for k, (r, c) in enumerate(zip(decoded, n_changed)):
+                rows.append({"input_sentence": sentence, "position": int(pos), "code": k, "own_code": k == out["own_code"],
+                             "recon_sentence": r, "n_changed_tokens": int(c)})
+    return rows
+
+
+def main():
+    import pandas as pd
+    if not torch.cuda.is_available():
+        raise SystemExit("the analysis needs an MI355X: the encoder, quantiser and decoder kernels have no CPU fallback")
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+    run_dir = RUN_DIR or f"./runs/{MODEL_NAME}/{RUN_ID}"
+    src = DECODED_SENTENCES_DF_PATH or f"{run_dir}/decoded_sentences_max_acc_only.feather"
+    try:
+        sentences_df = read_table(src)                                                       # :39
+    except FileNotFoundError:
+        sentences_df = corpus_table(SENTENCES_PATH, LATENT_CLASSES_LABELS_PATH, SYNTHETIC_SENTENCES)
+    all_gen_fact = sentences_df[sentences_df[GENERATIVE_FACTOR] == FACTOR_VALUE]["input_sentence"].tolist()[:OVERRIDE_TOT]   # :70-89
+    if not all_gen_fact:
+        raise SystemExit(f"no sentence with {GENERATIVE_FACTOR} == {FACTOR_VALUE!r} in the table")
+    torch.manual_seed(0)
+    if VQ_MODE == "VectorQuantizer":
+        vq = VectorQuantizer(n_e=VQ_N_E, e_dim=VQ_E_DIM, beta=VQ_BETA, vq_codebook_init_values=None)
+        vq.materialize_min_encodings = False
+    elif VQ_MODE == "MultiVectorQuantizer":
+        vq = MultiVectorQuantizer(n_factors=VQ_N_FACTORS, n_e=VQ_N_E, e_dim=VQ_E_DIM, beta=VQ_BETA)
+    else:
+        raise ValueError(f"{VQ_MODE} vector quantizer mode NOT supported here. Supported: VectorQuantizer, MultiVectorQuantizer")
+    model = Shelgon(encoder_model_name=ENCODER_MODEL_NAME, vector_quantizer=vq, decoder_model_name=DECODER_MODEL_NAME,
+                    compute_dtype=getattr(torch, COMPUTE_DTYPE)).to(device)                  # :45-55
+    if CKPT_PATH:
+        model.load_state_dict(torch.load(CKPT_PATH, map_location=device)["model_state_dict"])
+    model.eval()
+    torch.set_grad_enabled(False)                                                            # :42
+    tokenizer = load_tokenizer(TOKENIZER_NAME)
+    rows = code_traversal(model, tokenizer, all_gen_fact, device, TOKENIZED_SENTENCE_MAX_LENGTH, POSITIONS, FACTOR_INDEX,
+                          TOKENIZER_ADD_SPECIAL_TOKENS)
+    results_dir = RESULTS_DIR or run_dir
+    os.makedirs(results_dir, exist_ok=True)
+    written = write_table(pd.DataFrame(rows), f"{results_dir}/code_traversal.feather")
+    print(f"{len(all_gen_fact)} sentences, {len(rows)} variants -> {written}")
+    return rows
+
+
+if __name__ == "__main__":
+    main()

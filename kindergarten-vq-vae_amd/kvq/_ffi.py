@@ -127,6 +127,10 @@ SIGNATURES = {
     "kvq_dropout": (_int, [_vp, _i64, _f32, C.c_uint64, C.c_uint32, _int, _vp, _vp]),
     "kvq_zero_ranges": (_int, [C.POINTER(_vp), C.POINTER(_i64), _int, _vp]),
     "kvq_code_census": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp]),
+    "kvq_latent_group_sum_workspace_bytes": (_sz, [_i64, _int, _int, _int]),
+    "kvq_latent_group_sum": (_int, [_vp, _i64, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kvq_latent_shift": (_int, [_vp, _i64, _vp, _vp, _int, _int, C.c_double, _vp, _i64, _int, _int, _int, _int, _vp, _i64, _vp]),
+    "kvq_vq_lookup": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 """Device-resident census tables: the word x code census of the quantiser's indices (host side of `kvq_code_census`,
-include/kvq.h) and, at the end of the file, the attention-map census (`AttentionCensus`, host side of `kvq_attn_probs`).
+include/kvq.h), the attention-map census (`AttentionCensus`, host side of `kvq_attn_probs`) and, at the end of the file, the
+group means of encoder outputs (`LatentCensus`, host side of `kvq_latent_group_sum` / `kvq_latent_shift`).
 
 Boundary mirrored: the bookkeeping of analyses/unsupervised_vq_disentanglement/unsupervised_vq_disentanglement.py:156-235.
 The reference walks sentence -> word -> token in Python, tokenising every word of every sentence again to learn how many
@@ -160,3 +161,96 @@ class AttentionCensus:
         if self.count < 1:
             raise KvqError("AttentionCensus.results: no sentence was added")
         return {f: (t.cpu() / self.count).to(torch.float32) for f, t in self.tables.items()}
+
+
+class LatentCensus:
+    """Per-group sums of encoder outputs, one f64 table [n_groups, S, H] and one int64 count per group on the device -- the means
+    analyses/latent_arithmetics/latent_arithmetics_Bagon.py:97-131 takes over host copies of every encoder output ("300 sentences
+    per group"), with no limit on batches or sentences.  add() is one kvq_latent_group_sum per batch (f64, no float atomics, the
+    same bits on every run) and never synchronises; results() reads tables, counts and the bad-label word back once.
+    direction(g1, g0) = mean(g1) - mean(g0) on the host; shift() adds alpha times that difference to latents on the device
+    (kvq_latent_shift), which is what the reference feeds the decoder as encoder_hidden_states."""
+
+    def __init__(self, n_groups: int, S: int, H: int, device=None):
+        if n_groups < 1 or S < 1 or H < 1:
+            raise KvqError("LatentCensus: n_groups, S, H >= 1")
+        self.G, self.S, self.H = int(n_groups), int(S), int(H)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise KvqError("LatentCensus: the tables live on the GPU (no CPU path)")
+        self.table = torch.zeros((self.G, self.S, self.H), dtype=torch.float64, device=self.device)
+        self.count = torch.zeros(self.G, dtype=torch.int64, device=self.device)
+        self._bad = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._host = None                     # results() of the tables as they are now
+        self.sentences = 0                    # handed to add(), skipped ones included
+
+    def _check_latents(self, latents, what):
+        require_gpu(latents)
+        if latents.dim() != 3 or tuple(latents.shape[1:]) != (self.S, self.H):
+            raise KvqError(f"LatentCensus.{what}: latents must be [B, {self.S}, {self.H}], got {tuple(latents.shape)}")
+        if latents.dtype not in (torch.float32, torch.bfloat16):
+            raise KvqError(f"LatentCensus.{what}: latents must be float32 or bfloat16, got {latents.dtype}")
+        if latents.device != self.device:
+            raise KvqError(f"LatentCensus.{what}: latents on {latents.device}, tables on {self.device}")
+
+    def add(self, latents: torch.Tensor, group) -> None:
+        """latents [B, S, H] (f32 / bf16, on the device); group: one label for the whole batch, or [B] integer labels (a tensor
+        on either side, or a sequence): -1 = leave the sentence out, 0 .. n_groups-1 = its group.  A label outside that range is
+        found by results()."""
+        from . import nnops
+        self._check_latents(latents, "add")
+        B = latents.shape[0]
+        if isinstance(group, int):
+            group = torch.full((B,), group, dtype=torch.int32, device=self.device)
+        elif not torch.is_tensor(group):
+            group = torch.tensor(list(group), dtype=torch.int32)
+        if group.dim() != 1 or group.numel() != B or group.is_floating_point() or group.dtype == torch.bool:
+            raise KvqError(f"LatentCensus.add: group must be an int or {B} integer labels")
+        group = group.to(device=self.device, dtype=torch.int32).contiguous()
+        if B == 0:
+            return
+        nnops.latent_group_sum(latents, group, self.table, self.count, self._bad)
+        self._host = None
+        self.sentences += B
+
+    def results(self) -> dict:
+        """dict(mean = float64 [n_groups, S, H] (zeros for an empty group), count = int64 [n_groups]) on the host."""
+        if self._host is None:
+            n = self.G * self.S * self.H
+            # one read-back: the table, then counts and the bad-label word as their exact f64 values (counts stay below 2^53)
+            flat = torch.cat([self.table.reshape(-1), self.count.to(torch.float64), self._bad.to(torch.float64)]).cpu()
+            bad = int(flat[n + self.G].item()) & 0xFFFFFFFF
+            if bad:
+                raise KvqError(f"LatentCensus: {bad} sentences carried a group label outside [-1, {self.G})")
+            count = flat[n:n + self.G].to(torch.int64)
+            mean = flat[:n].view(self.G, self.S, self.H) / count.clamp(min=1).to(torch.float64).view(-1, 1, 1)
+            self._host = dict(mean=mean, count=count)
+        return self._host
+
+    def _require_filled(self, what, *groups):
+        res = self.results()
+        for g in groups:
+            if not 0 <= int(g) < self.G:
+                raise KvqError(f"LatentCensus.{what}: group {g} outside [0, {self.G})")
+            if int(res["count"][int(g)]) == 0:
+                raise KvqError(f"LatentCensus.{what}: group {g} is empty")
+        return res
+
+    def direction(self, g1: int, g0: int) -> torch.Tensor:
+        """mean(g1) - mean(g0), float64 [S, H] on the host."""
+        res = self._require_filled("direction", g1, g0)
+        return res["mean"][int(g1)] - res["mean"][int(g0)]
+
+    def shift(self, latents: torch.Tensor, g1: int, g0: int, alpha: float = 1.0, sel=None, out=None) -> torch.Tensor:
+        """latents + alpha * (mean(g1) - mean(g0)) at the positions with sel[b, s] != 0 (sel: [B, S] bool / int8 on the device, None
+        = every position), the unchanged bits elsewhere; f64 arithmetic rounded to f32, then to the latents' dtype.  out=latents
+        shifts in place.  An empty group is refused (the counts are known from results())."""
+        from . import nnops
+        self._check_latents(latents, "shift")
+        self._require_filled("shift", g1, g0)
+        if sel is not None:
+            require_gpu(sel)
+            if tuple(sel.shape) != tuple(latents.shape[:2]):
+                raise KvqError(f"LatentCensus.shift: sel must be [B, S] = {tuple(latents.shape[:2])}, got {tuple(sel.shape)}")
+            sel = (sel != 0).to(torch.int8).contiguous()
+        return nnops.latent_shift(latents, self.table, self.count, int(g1), int(g0), float(alpha), sel=sel, out=out)

@@ -1189,20 +1189,28 @@ class TrainEngine:
     # one training step
     # ------------------------------------------------------------------------------------------------------------
     def forward_backward(self, input_ids, attention_mask, training=True, compute_grads=True, dec_ids=None, dec_mask=None,
-                         want_logits=False, quantizer_training=None, stop_after_quantizer=False, defer_backward=False, target_ids=None):
+                         want_logits=False, quantizer_training=None, stop_after_quantizer=False, defer_backward=False, target_ids=None,
+                         latents=None, stop_after_encoder=False, skip_quantizer=False, want_latents=False):
         """Forward (+ backward when compute_grads).  Returns dict(loss_recon, loss_vq, perplexity, acc, acc_per_sentence,
         recon_ids, indices [, logits]).  dec_ids / dec_mask: the decoder's own input (Bagon.forward takes one, and the Bagon step
         tokenises and perturbs the two sides separately, models/bagon/Trainer.py:78-96; default = the encoder's).  target_ids:
         what the loss and the accuracy score the logits against (default = the decoder's input, as models/bagon/Trainer.py:103-110
         and models/shelgon3/Trainer.py:94-101 do).
         defer_backward (with compute_grads=False): the forward's activations stay alive and out["_resume"] can be handed to
-        backward_from() once the gradient of the returned logits is known (kvq.engine.engine_autograd_forward)."""
+        backward_from() once the gradient of the returned logits is known (kvq.engine.engine_autograd_forward).
+        The latent calls (encode / decode below; forward-only, None / False everywhere else) enter and leave the same schedule:
+        latents [B, Se, H] replaces the encoder's output (input_ids / attention_mask are not read and may be None),
+        stop_after_encoder returns before the quantiser, skip_quantizer hands the encoder output (or `latents`) to the decoder as it
+        is, want_latents adds z / z_q to what stop_after_quantizer returns."""
         self._stop_after_quantizer = bool(stop_after_quantizer) and not compute_grads
-        S = max(input_ids.shape[1], dec_ids.shape[1] if dec_ids is not None else 0)
+        if (latents is not None or stop_after_encoder or skip_quantizer or want_latents) and (compute_grads or defer_backward):
+            raise KvqError("TrainEngine: latents / stop_after_encoder / skip_quantizer / want_latents are forward-only arguments")
+        enc_shape = tuple(latents.shape[:2]) if latents is not None else tuple(input_ids.shape)
+        S = max(enc_shape[1], dec_ids.shape[1] if dec_ids is not None else 0)
         if S > (128 if self.dtype == torch.bfloat16 else 32):
             raise KvqError(f"TrainEngine: sequence length {S} above the attention kernels' limit (32 tokens in f32, 128 in bf16 "
                            f"through the blocked kernels; use the autograd path)")
-        if dec_ids is not None and (dec_mask is None or dec_ids.shape[0] != input_ids.shape[0] or dec_mask.shape != dec_ids.shape):
+        if dec_ids is not None and (dec_mask is None or dec_ids.shape[0] != enc_shape[0] or dec_mask.shape != dec_ids.shape):
             raise KvqError("TrainEngine: dec_ids needs a dec_mask of its shape and the encoder's batch size")
         if target_ids is not None and target_ids.shape != (dec_ids if dec_ids is not None else input_ids).shape:
             raise KvqError("TrainEngine: target_ids must have the shape of the decoder's input")
@@ -1220,7 +1228,9 @@ class TrainEngine:
                 if self.fp8:
                     self._x8.clear()
                 out = self._forward_backward(input_ids, attention_mask, training, compute_grads, dec_ids, dec_mask, want_logits,
-                                             defer=bool(defer_backward), target_ids=target_ids)
+                                             defer=bool(defer_backward), target_ids=target_ids, latents=latents,
+                                             stop_after_encoder=bool(stop_after_encoder), skip_quantizer=bool(skip_quantizer),
+                                             want_latents=bool(want_latents))
                 if defer_backward:
                     out["_resume"] = dict(gen=out.pop("_gen"), sorted_ids=self._sorted, step=self._step_host,
                                           versions=self._versions())
@@ -1312,9 +1322,143 @@ class TrainEngine:
             census.count += B
         return stacks
 
+    # ------------------------------------------------------------------------------------------------------------
+    # latent analyses: the schedule of forward_logits entered / left at the latent (evaluation mode, eager, one process)
+    # ------------------------------------------------------------------------------------------------------------
+    _TRAVERSE_CHUNK = 256               # variants per decode of traverse_codes
+
+    def _latent_call(self, what):
+        """What encode / decode / decode_codes / traverse_codes refuse, before anything is launched."""
+        if self._cap is not None or torch.cuda.is_current_stream_capturing():
+            raise KvqError(f"TrainEngine.{what} is an eager call: not under graph capture")
+        if self.group is not None or self._dp:
+            raise KvqError(f"TrainEngine.{what} is a single-process call (this engine has a process group)")
+        if self.fp8:
+            raise KvqError(f"TrainEngine.{what}: not on an fp8 engine -- its GEMMs read fp8 copies that the kernel producing an "
+                           f"activation writes beside it, and a latent handed in from outside has no such producer-written copy")
+        self.refresh_if_params_changed()
+        if getattr(self, "_epack", None) is not None:
+            self._E_version = None
+
+    def _seq_limit(self, what, *lengths):
+        lim = 128 if self.dtype == torch.bfloat16 else 32
+        if max(lengths) > lim:
+            raise KvqError(f"TrainEngine.{what}: sequence length {max(lengths)} above the attention kernels' limit ({lim} tokens "
+                           f"in {'bf16' if lim == 128 else 'f32'})")
+
+    def encode(self, enc_ids, enc_mask, quantize=True):
+        """The latent of a batch: dict(z [B, S, H] = the encoder's output in the engine's dtype) and, for a model with a quantiser
+        and quantize=True, z_q [B, S, H], indices (as forward_logits returns them), perplexity, loss_vq_raw -- the quantiser in
+        evaluation mode.  What analyses/latent_arithmetics/latent_arithmetics_Bagon.py:92 takes from the HF encoder and
+        analyses/latent_traversals/latent_traversals_Shelgon_latent_classes.py:120-126 from encoder + quantiser."""
+        self._latent_call("encode")
+        if enc_ids.dim() != 2 or enc_mask.shape != enc_ids.shape:
+            raise KvqError("TrainEngine.encode: enc_ids [B, S] needs an enc_mask of its shape")
+        self._seq_limit("encode", enc_ids.shape[1])
+        if self.has_vq and quantize:
+            return self.forward_backward(enc_ids, enc_mask, training=False, compute_grads=False, quantizer_training=False,
+                                         stop_after_quantizer=True, want_latents=True)
+        return self.forward_backward(enc_ids, enc_mask, training=False, compute_grads=False, stop_after_encoder=True)
+
+    def decode(self, latents, dec_ids, dec_mask, target_ids=None, quantize=False, want_logits=False):
+        """The decoder and LM head of forward_logits on a latent of the caller's choosing: latents [B, Se, H] (the engine's dtype,
+        contiguous) is the cross-attention source (HF's encoder_hidden_states, latent_arithmetics_Bagon.py:133-137); Se may differ
+        from the decoder's length.  quantize=True sends the latents through the quantiser (evaluation mode) first -- the caller
+        edits z -- and the result then carries `indices`.  Returns dict(recon_ids [B, Sd], acc, acc_per_sentence [B], loss_recon
+        [, logits [B, Sd, V]] [, indices]), scored against target_ids (default: dec_ids) by the kvq_ce_forward path."""
+        self._latent_call("decode")
+        if not torch.is_tensor(latents) or latents.dim() != 3 or latents.shape[2] != self.H:
+            raise KvqError(f"TrainEngine.decode: latents must be [B, Se, {self.H}], got "
+                           f"{tuple(latents.shape) if torch.is_tensor(latents) else type(latents).__name__}")
+        if latents.dtype != self.dtype or latents.device != self.dev or not latents.is_contiguous():
+            raise KvqError(f"TrainEngine.decode: latents must be contiguous {self.dtype} on {self.dev}, got {latents.dtype} on {latents.device}")
+        if dec_ids.dim() != 2 or dec_ids.shape[0] != latents.shape[0]:
+            raise KvqError(f"TrainEngine.decode: {latents.shape[0]} latents but dec_ids {tuple(dec_ids.shape)}")
+        if dec_mask is None or dec_mask.shape != dec_ids.shape:
+            raise KvqError("TrainEngine.decode: dec_ids needs a dec_mask of its shape")
+        if quantize and not self.has_vq:
+            raise KvqError("TrainEngine.decode: quantize=True, but the model has no quantiser")
+        self._seq_limit("decode", latents.shape[1], dec_ids.shape[1])
+        out = self.forward_backward(None, None, training=False, compute_grads=False, dec_ids=dec_ids, dec_mask=dec_mask,
+                                    want_logits=want_logits, quantizer_training=False, target_ids=target_ids, latents=latents,
+                                    skip_quantizer=not quantize)
+        res = {k: out[k] for k in ("recon_ids", "acc", "acc_per_sentence", "loss_recon")}
+        if want_logits:
+            res["logits"] = out["logits"]
+        if quantize:
+            res["indices"] = out["indices"]
+        return res
+
+    def _code_rows(self, what, indices):
+        """indices [B, Se] / [B, Se, G] int64 -> the contiguous [B, Se, G] the lookup kernel reads."""
+        if self.vq_kind not in ("VectorQuantizer", "MultiVectorQuantizer"):
+            raise KvqError(f"TrainEngine.{what}: needs a VectorQuantizer or MultiVectorQuantizer codebook (this model has "
+                           f"{self.vq_kind or 'no quantiser'})")
+        if not torch.is_tensor(indices) or indices.dtype != torch.int64 or indices.device != self.dev:
+            raise KvqError(f"TrainEngine.{what}: indices must be an int64 tensor on {self.dev}")
+        if indices.dim() == 2 and self.G == 1:
+            indices = indices.unsqueeze(-1)
+        if indices.dim() != 3 or indices.shape[2] != self.G:
+            raise KvqError(f"TrainEngine.{what}: indices must be [B, Se, {self.G}]" + (" or [B, Se]" if self.G == 1 else "")
+                           + f", got {tuple(indices.shape)}")
+        return indices.contiguous()
+
+    def codes_to_latents(self, indices):
+        """z_q [B, Se, H] in the engine's dtype = the codebook rows of indices [B, Se] / [B, Se, G] (kvq_vq_lookup): the row itself,
+        not the straight-through value the quantiser's forward hands on.  An index outside [0, K) raises."""
+        idx = self._code_rows("codes_to_latents", indices)
+        B, Se, G = idx.shape
+        bad = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        rows = nnops.vq_lookup(idx.view(B * Se, G), self.E.data, self.K, self.dtype, n_bad=bad)
+        if int(bad.item()):
+            raise KvqError(f"TrainEngine.codes_to_latents: {int(bad.item())} indices outside [0, {self.K})")
+        vq = self.model.vector_quantizer
+        if getattr(vq, "ragged", False):             # padded slices back to the e_dim columns (MultiVectorQuantizer.merge)
+            rows = rows.index_select(1, vq.inv_map)
+        return rows.view(B, Se, self.H)
+
+    def decode_codes(self, indices, dec_ids, dec_mask, target_ids=None, want_logits=False):
+        """decode() of the codebook rows of `indices` [B, Se] / [B, Se, G] int64: what
+        latent_traversals_Shelgon_latent_classes.py:139-150 does after overwriting the discrete latent by hand."""
+        self._latent_call("decode_codes")
+        return self.decode(self.codes_to_latents(indices), dec_ids, dec_mask, target_ids=target_ids, want_logits=want_logits)
+
+    def traverse_codes(self, enc_ids, enc_mask, sentence, position, dec_ids=None, dec_mask=None, factor=0):
+        """Every code at one place of one sentence: encodes the batch, takes sentence `sentence`'s own index rows [Se, G], builds the
+        K variants that differ from them only at (position, factor) -- variant k carries code k there -- and decodes them with
+        that sentence's decoder ids (default: its encoder ids), at most 256 variants per launch sequence.
+        Returns dict(recon_ids [K, Sd], own_code (int), changed [K, Sd] bool: tokens that differ from the own code's row)."""
+        self._latent_call("traverse_codes")
+        if self.vq_kind not in ("VectorQuantizer", "MultiVectorQuantizer"):
+            raise KvqError(f"TrainEngine.traverse_codes: needs a VectorQuantizer or MultiVectorQuantizer codebook (this model has "
+                           f"{self.vq_kind or 'no quantiser'})")
+        d_ids = enc_ids if dec_ids is None else dec_ids
+        d_mask = enc_mask if dec_mask is None else dec_mask
+        B, Se = enc_ids.shape
+        if not (0 <= int(sentence) < B and 0 <= int(position) < Se and 0 <= int(factor) < self.G):
+            raise KvqError(f"TrainEngine.traverse_codes: (sentence, position, factor) = ({sentence}, {position}, {factor}) outside "
+                           f"({B}, {Se}, {self.G})")
+        if d_ids.shape[0] != B or d_mask.shape != d_ids.shape:
+            raise KvqError("TrainEngine.traverse_codes: dec_ids needs the encoder's batch size and a dec_mask of its shape")
+        own = self.encode(enc_ids, enc_mask)["indices"].reshape(B, Se, self.G)[int(sentence)]
+        own_code = int(own[int(position), int(factor)].item())
+        K = self.K
+        rows = own.unsqueeze(0).repeat(K, 1, 1)
+        rows[:, int(position), int(factor)] = torch.arange(K, dtype=torch.int64, device=self.dev)
+        recon = []
+        for k0 in range(0, K, self._TRAVERSE_CHUNK):
+            n = min(self._TRAVERSE_CHUNK, K - k0)
+            out = self.decode_codes(rows[k0:k0 + n], d_ids[int(sentence)].unsqueeze(0).expand(n, -1).contiguous(),
+                                    d_mask[int(sentence)].unsqueeze(0).expand(n, -1).contiguous())
+            recon.append(out["recon_ids"])
+        recon = torch.cat(recon)
+        return dict(recon_ids=recon, own_code=own_code, changed=recon != recon[own_code].unsqueeze(0))
+
     def _forward_backward(self, input_ids, attention_mask, training, compute_grads, dec_ids=None, dec_mask=None, want_logits=False,
-                          defer=False, target_ids=None):
-        gen = self._fb_gen(input_ids, attention_mask, training, compute_grads, dec_ids, dec_mask, want_logits, defer, target_ids)
+                          defer=False, target_ids=None, latents=None, stop_after_encoder=False, skip_quantizer=False,
+                          want_latents=False):
+        gen = self._fb_gen(input_ids, attention_mask, training, compute_grads, dec_ids, dec_mask, want_logits, defer, target_ids,
+                           latents, stop_after_encoder, skip_quantizer, want_latents)
         try:
             out = next(gen)                 # only a deferred call yields: forward done, the generator holds the activations
         except StopIteration as done:
@@ -1362,12 +1506,13 @@ class TrainEngine:
                 out[a["p"]] = torch.empty_like(a["p"]).copy_(a["g"].reshape(a["p"].shape))
         return out
 
-    def _fb_gen(self, input_ids, attention_mask, training, compute_grads, dec_ids, dec_mask, want_logits, defer, target_ids=None):
+    def _fb_gen(self, input_ids, attention_mask, training, compute_grads, dec_ids, dec_mask, want_logits, defer, target_ids=None,
+                latents=None, stop_after_encoder=False, skip_quantizer=False, want_latents=False):
         m = self.model
         fl, H = self.flat, self.H
-        B, S = input_ids.shape
+        B, S = latents.shape[:2] if latents is not None else input_ids.shape
         N = B * S
-        mask = attention_mask.contiguous()
+        mask = attention_mask.contiguous() if attention_mask is not None else None
         ecfg, dcfg = self.ecfg, self.dcfg
         d_ids = input_ids if dec_ids is None else dec_ids
         d_mask = mask if dec_mask is None else dec_mask.contiguous()
@@ -1377,15 +1522,22 @@ class TrainEngine:
             raise KvqError("TrainEngine: encoder and decoder batches differ")
 
         # ---------------- forward ----------------
-        x, emb_saved = self._emb_fwd("enc.emb.", ecfg, input_ids, training)
         enc_saved = []
-        for i in range(self.n_enc_layers):
-            x, sa = self._attn_block_fwd(f"enc.{i}.sa.", x, None, mask, False, ecfg, training, B, S, S, next_key=f"enc.{i}.f1.w")
-            x, ff = self._ffn_fwd(f"enc.{i}.", x, ecfg, training, next_key=f"enc.{i + 1}.sa.q.w" if i + 1 < self.n_enc_layers else None)
-            enc_saved.append((sa, ff))
+        if latents is not None:             # decode(): the caller's latent stands where the encoder's output would
+            x, emb_saved = latents.view(N, H), None
+        else:
+            x, emb_saved = self._emb_fwd("enc.emb.", ecfg, input_ids, training)
+            for i in range(self.n_enc_layers):
+                x, sa = self._attn_block_fwd(f"enc.{i}.sa.", x, None, mask, False, ecfg, training, B, S, S, next_key=f"enc.{i}.f1.w")
+                x, ff = self._ffn_fwd(f"enc.{i}.", x, ecfg, training, next_key=f"enc.{i + 1}.sa.q.w" if i + 1 < self.n_enc_layers else None)
+                enc_saved.append((sa, ff))
         z = x
+        if stop_after_encoder:              # encode() without a quantiser, or with quantize=False
+            return dict(z=z.view(B, S, H))
         gum_saved = None
-        if self.vq_kind in ("VectorQuantizer", "MultiVectorQuantizer"):
+        if skip_quantizer:                  # decode(quantize=False) of a model with a quantiser: the latent goes to the decoder as it is
+            idx, loss_vq, perplexity, enc_out, indices = None, None, None, z, None
+        elif self.vq_kind in ("VectorQuantizer", "MultiVectorQuantizer"):
             cap = self._cap
             if cap is not None:                     # graph capture: the quantiser stays an eager launch between two graphs
                 z_q, idx, vq_out = cap.z_q, cap.idx, cap.vq_out
@@ -1403,6 +1555,8 @@ class TrainEngine:
         else:
             idx, loss_vq, perplexity, enc_out, indices = None, None, None, z, None
         if getattr(self, "_stop_after_quantizer", False):
+            if want_latents:                # encode()
+                return dict(z=z.view(B, S, H), z_q=enc_out.view(B, S, H), indices=indices, perplexity=perplexity, loss_vq_raw=loss_vq)
             return dict(indices=indices, perplexity=perplexity, loss_vq_raw=loss_vq)
 
         y, demb_saved = self._emb_fwd("dec.emb.", dcfg, d_ids, training, word_rows=None)
@@ -1448,11 +1602,11 @@ class TrainEngine:
                                        row_lse.data_ptr(), pred.data_ptr(), ce_out[0:].data_ptr(), ce_out[1:].data_ptr(), stream_ptr()),
                   "kvq_ce_forward")
         acc_sent = None
-        if self.sentence_acc:               # seq_acc's second result (common/metrics.py:32-36), read by the Bagon trainer's decode step
+        if self.sentence_acc or latents is not None:     # seq_acc's second result (common/metrics.py:32-36), read by the Bagon trainer's decode step
             acc_sent = torch.empty(B, dtype=torch.float32, device=self.dev)
             check(lib().kvq_seq_acc(pred.data_ptr(), tgt.data_ptr(), B, Sd, acc_sent.data_ptr(), stream_ptr()), "kvq_seq_acc")
         out = dict(loss_recon=ce_out[0] if self.w_recon == 1.0 else ce_out[0] * self.w_recon,
-                   loss_vq=(loss_vq if self.w_vq == 1.0 else loss_vq * self.w_vq) if self.has_vq else None,
+                   loss_vq=(loss_vq if self.w_vq == 1.0 else loss_vq * self.w_vq) if loss_vq is not None else None,
                    perplexity=perplexity, acc=ce_out[1], acc_per_sentence=acc_sent, recon_ids=pred.view(B, Sd), indices=indices)
         if want_logits:
             out["logits"] = logits[:, :self.V].reshape(B, Sd, self.V)

@@ -210,6 +210,85 @@ def attn_probs(q, k, v, mask, B, nh, Sq, Sk, causal, lse=None, probs=None, table
     return probs
 
 
+def _rows3(x, what):
+    """(B, S, H, row stride in elements) of an activation [B, S, H] whose (b, s) rows lie at one stride (a contiguous tensor, or a
+    column slice of one)."""
+    if x.dim() != 3 or x.stride(2) != 1 or (x.shape[0] > 1 and x.stride(0) != x.shape[1] * x.stride(1)):
+        raise KvqError(f"{what}: needs [B, S, H] activations with unit column stride and evenly strided rows, got shape "
+                       f"{tuple(x.shape)} strides {tuple(x.stride())}")
+    B, S, H = x.shape
+    return B, S, H, (x.stride(1) if S > 1 else max(x.stride(0), H))
+
+
+def latent_group_sum(x, group, table, count, n_bad=None):
+    """table [G, S, H] f64 += per-group sums of x [B, S, H] (f32 / bf16), count [G] int64 += sentences per group
+    (kvq_latent_group_sum).  group [B] int32: -1 skips a sentence; labels outside [-1, G) are skipped and counted in n_bad
+    ([1] int32, optional).  Deterministic: no float atomics."""
+    require_gpu(x, group, table, count, n_bad)
+    B, S, H, ldx = _rows3(x, "latent_group_sum")
+    G = table.shape[0] if table.dim() == 3 else -1
+    if table.dtype != torch.float64 or tuple(table.shape) != (G, S, H) or not table.is_contiguous():
+        raise KvqError(f"latent_group_sum: table must be a contiguous float64 [G, {S}, {H}], got {table.dtype} {tuple(table.shape)}")
+    if count.dtype != torch.int64 or tuple(count.shape) != (G,) or not count.is_contiguous():
+        raise KvqError(f"latent_group_sum: count must be a contiguous int64 [{G}]")
+    if group.dtype != torch.int32 or tuple(group.shape) != (B,) or not group.is_contiguous():
+        raise KvqError(f"latent_group_sum: group must be a contiguous int32 [{B}], got {group.dtype} {tuple(group.shape)}")
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1):
+        raise KvqError("latent_group_sum: n_bad must be one int32 word")
+    l = lib()
+    nws = l.kvq_latent_group_sum_workspace_bytes(B, S, H, G)
+    ws = _workspace(x.device, nws)               # slabs: written and consumed inside this call, on this stream
+    check(l.kvq_latent_group_sum(x.data_ptr(), ldx, group.data_ptr(), B, S, H, G, io_dtype_of(x), table.data_ptr(), count.data_ptr(),
+                                 _p(n_bad), ws.data_ptr(), nws, stream_ptr()), "kvq_latent_group_sum")
+
+
+def latent_shift(x, table, count, g1, g0, alpha=1.0, sel=None, out=None):
+    """out = x + alpha * (table[g1] / count[g1] - table[g0] / count[g0]) at the positions with sel[b, s] != 0 (sel [B, S] int8, None
+    = all), x elsewhere (kvq_latent_shift: f64 arithmetic -> f32 -> the dtype of x).  out: None = a new tensor, or x itself."""
+    require_gpu(x, table, count, sel, out)
+    B, S, H, ldx = _rows3(x, "latent_shift")
+    G = table.shape[0] if table.dim() == 3 else -1
+    if table.dtype != torch.float64 or tuple(table.shape) != (G, S, H) or not table.is_contiguous():
+        raise KvqError(f"latent_shift: table must be a contiguous float64 [G, {S}, {H}], got {table.dtype} {tuple(table.shape)}")
+    if count.dtype != torch.int64 or tuple(count.shape) != (G,) or not count.is_contiguous():
+        raise KvqError(f"latent_shift: count must be a contiguous int64 [{G}]")
+    if not (0 <= int(g1) < G and 0 <= int(g0) < G):
+        raise KvqError(f"latent_shift: groups {g1}, {g0} outside [0, {G})")
+    if sel is not None and (sel.dtype != torch.int8 or tuple(sel.shape) != (B, S) or not sel.is_contiguous()):
+        raise KvqError(f"latent_shift: sel must be a contiguous int8 [{B}, {S}], got {sel.dtype} {tuple(sel.shape)}")
+    if out is None:
+        out = torch.empty((B, S, H), dtype=x.dtype, device=x.device)
+    if out.dtype != x.dtype or tuple(out.shape) != (B, S, H):
+        raise KvqError("latent_shift: out must have the shape and dtype of x")
+    ldo = _rows3(out, "latent_shift (out)")[3]
+    check(lib().kvq_latent_shift(x.data_ptr(), ldx, table.data_ptr(), count.data_ptr(), int(g1), int(g0), float(alpha), _p(sel), B, S, H, G,
+                                 io_dtype_of(x), out.data_ptr(), ldo, stream_ptr()), "kvq_latent_shift")
+    return out
+
+
+def vq_lookup(indices, codebook, n_codes, dtype, out=None, n_bad=None):
+    """out [N, G * Dg] (dtype f32 / bf16) = the codebook rows of indices [N, G] int64: out[n, g*Dg:(g+1)*Dg] = codebook[g*K + idx[n, g]]
+    for the f32 codebook [G * K, Dg] (the `embedding.weight` layout of VectorQuantizer / MultiVectorQuantizer) -- kvq_vq_lookup.
+    An index outside [0, K) leaves a zero row and is counted in n_bad ([1] int32, optional)."""
+    require_gpu(indices, codebook, out, n_bad)
+    if indices.dtype != torch.int64 or indices.dim() != 2 or not indices.is_contiguous():
+        raise KvqError(f"vq_lookup: indices must be a contiguous int64 [N, G], got {indices.dtype} {tuple(indices.shape)}")
+    N, G = indices.shape
+    K = int(n_codes)
+    if codebook.dtype != torch.float32 or codebook.dim() != 2 or codebook.shape[0] != G * K or not codebook.is_contiguous():
+        raise KvqError(f"vq_lookup: the codebook must be a contiguous float32 [{G} * {K}, Dg], got {codebook.dtype} {tuple(codebook.shape)}")
+    Dg = codebook.shape[1]
+    if out is None:
+        out = torch.empty((N, G * Dg), dtype=dtype, device=indices.device)
+    if out.dtype != dtype or tuple(out.shape) != (N, G * Dg) or out.stride(1) != 1:
+        raise KvqError(f"vq_lookup: out must be {dtype} [{N}, {G * Dg}] with unit column stride")
+    if n_bad is not None and (n_bad.dtype != torch.int32 or n_bad.numel() != 1):
+        raise KvqError("vq_lookup: n_bad must be one int32 word")
+    check(lib().kvq_vq_lookup(indices.data_ptr(), codebook.data_ptr(), N, K, Dg, G, io_dtype_of(out), out.data_ptr(),
+                              out.stride(0) if N > 1 else max(out.stride(0), G * Dg), _p(n_bad), stream_ptr()), "kvq_vq_lookup")
+    return out
+
+
 def attn_fwd_fp8_ok(Sq, Sk):
     return bool(lib().kvq_attn_fwd_fp8_ok(int(Sq), int(Sk)))
 

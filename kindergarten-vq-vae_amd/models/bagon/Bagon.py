@@ -142,6 +142,20 @@ class Bagon(nn.Module):
         return engine_of(self).attention_maps(encoder_input_ids, encoder_attention_mask, decoder_input_ids, decoder_attention_mask,
                                               census=census, per_sentence=per_sentence)
 
+    def encode_latents(self, input_ids, attention_mask, quantize=True):
+        """TrainEngine.encode: dict(z [B, S, H]) -- the encoder output in the compute dtype, on the engine's kernels (evaluation
+        mode); a model with a quantiser adds z_q, indices, perplexity, loss_vq_raw unless quantize=False.  No ATen path."""
+        from kvq.engine import engine_of
+        return engine_of(self).encode(input_ids, attention_mask, quantize=quantize)
+
+    def decode_latents(self, latents, decoder_input_ids, decoder_attention_mask, target_ids=None, quantize=False, want_logits=False):
+        """TrainEngine.decode: the decoder and LM head on latents [B, Se, H] of the caller's choosing (HF's encoder_hidden_states,
+        analyses/latent_arithmetics/latent_arithmetics_Bagon.py:133-137): dict(recon_ids, acc, acc_per_sentence, loss_recon
+        [, logits] [, indices]).  quantize=True (a model with a quantiser) sends the latents through it first."""
+        from kvq.engine import engine_of
+        return engine_of(self).decode(latents, decoder_input_ids, decoder_attention_mask, target_ids=target_ids, quantize=quantize,
+                                      want_logits=want_logits)
+
     def forward_loss(self, encoder_input_ids, encoder_attention_mask, decoder_input_ids, decoder_attention_mask):
         """Fused step body of the plain autoencoder: (loss_recon, acc_per_batch, recon_ids) -- the loss block of
         models/bagon/Trainer.py:103-110 in one pass over the logits."""

@@ -83,6 +83,21 @@ class Shelgon(Bagon):
         reading the quantised encoder output."""
         return super().attention_maps(input_ids, attention_mask, census=census, per_sentence=per_sentence)
 
+    def decode_codes(self, indices, decoder_input_ids, decoder_attention_mask, target_ids=None, want_logits=False):
+        """TrainEngine.decode_codes: decode_latents of the codebook rows of indices [B, Se] / [B, Se, G] -- the hand-written discrete
+        latent of analyses/latent_traversals/latent_traversals_Shelgon_latent_classes.py:139-150."""
+        from kvq.engine import engine_of
+        return engine_of(self).decode_codes(indices, decoder_input_ids, decoder_attention_mask, target_ids=target_ids,
+                                            want_logits=want_logits)
+
+    def traverse_codes(self, input_ids, attention_mask, sentence, position, decoder_input_ids=None, decoder_attention_mask=None,
+                       factor=0):
+        """TrainEngine.traverse_codes: the reconstructions of one sentence under every code at (position, factor):
+        dict(recon_ids [K, Sd], own_code, changed [K, Sd])."""
+        from kvq.engine import engine_of
+        return engine_of(self).traverse_codes(input_ids, attention_mask, sentence, position, dec_ids=decoder_input_ids,
+                                              dec_mask=decoder_attention_mask, factor=factor)
+
     def forward_loss(self, input_ids, attention_mask):
         """Fused step body: (vq_loss, perplexity, indices, loss_recon, acc_per_batch, recon_ids)."""
         embeds = self.encode(input_ids, attention_mask)
