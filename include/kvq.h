@@ -167,6 +167,8 @@ int kvq_vq_ema_update(const void* z, const int64_t* idx, int64_t N, int K, int D
  *   logits [N,V] io dtype ; target [N] int64 ; row_loss [N] f32 ; row_lse [N] f32 ; pred [N] int64
  *   loss [1] f32 = mean(row_loss) ; acc [1] f32 = mean(pred == target)  (common/metrics.py:18-30)
  * The [N,V] one-hot of the reference (1 GB at N=8192) is never built.
+ * Logits of -inf are allowed off the target: they add 0 to the row's sum, row_lse stays finite and their gradient is exactly 0.
+ * A row whose target logit is -inf has row_loss = +inf (and so has the mean).  +inf and NaN logits are not supported.
  */
 int kvq_ce_forward(const void* logits, const int64_t* target, int64_t N, int V, int64_t ld, int io_dtype,
                    float* row_loss, float* row_lse, int64_t* pred, float* loss, float* acc, void* stream);

@@ -8,6 +8,7 @@
 // HBM-bound: forward reads N*V elements once; backward reads and writes them once (in place allowed).
 // One workgroup per row; rows are only 4-byte aligned (V = 30522), so each row is walked as
 // scalar head | 16-byte vectors | scalar tail.
+#include <float.h>
 #include <math.h>
 
 #include "kvq_common.h"
@@ -52,6 +53,10 @@ struct MaxSum {
     float bv;     // best value for argmax
     int bi;       // its (lowest) index
 };
+// The running maximum starts at the lowest FINITE float, not at -inf: a -inf logit met first then adds exp(-inf - m) = 0 instead
+// of exp(-inf - (-inf)) = NaN, without a branch per element.  Finite inputs give the same bits as a -inf start: the first
+// finite x takes the `x > m` arm (or equals m) and rescales a sum that is still 0, and a thread that saw nothing merges as 0.
+#define KVQ_CE_MAXSUM_INIT {-FLT_MAX, 0.f, -INFINITY, INT_MAX}
 
 __device__ __forceinline__ void ms_push(MaxSum& a, float x, int i) {
     if (x > a.m) { a.s = a.s * __expf(a.m - x) + 1.0f; a.m = x; }
@@ -95,7 +100,7 @@ __global__ __launch_bounds__(CE_THREADS) void ce_fwd_kernel(const void* __restri
     const int t = threadIdx.x;
     RowWalk<DT> rw(logits, n, V, ld);
     constexpr int VEC = RowWalk<DT>::VEC;
-    MaxSum a = {-INFINITY, 0.f, -INFINITY, INT_MAX};
+    MaxSum a = KVQ_CE_MAXSUM_INIT;
     if (t < rw.head) ms_push(a, IO<DT>::load1(rw.base, t), t);
     for (int q = t; q < rw.nvec; q += CE_THREADS) {
         float v[VEC];

@@ -682,9 +682,12 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
     const float pdf = 0.39894228040143268f * __expf(-0.5f * x * x);
     return cdf + x * pdf;
 }
-// bf16 io: erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, far below the bf16 rounding of the result) -- libm's erff
-// makes these kernels VALU-bound (~40 instructions per element) instead of HBM-bound.  exp(-x^2/2) is shared between the
-// erf tail and the Gaussian density of the derivative.
+// bf16 io: erf by Abramowitz & Stegun 7.1.26 -- libm's erff makes these kernels VALU-bound (~40 instructions per element)
+// instead of HBM-bound.  exp(-x^2/2) is shared between the erf tail and the Gaussian density of the derivative.
+// The formula's error is ABSOLUTE: at most 1.5e-7 on erf, 0.7e-7 on the CDF (measured: profiles/pointwise_parity.md).  That is
+// below the bf16 rounding of gelu(x) for x > -5.19 (the first stored value more than one bf16 ulp off is x = -5.1875); further
+// down the negative tail the CDF itself falls below 1e-7 and the relative error of the result grows (4 % at x = -13.1) while
+// staying negligible in absolute terms (< 1.4e-7 |x|).
 __device__ __forceinline__ void gelu_parts_fast(float x, float& cdf, float& e) {
     const float z = fabsf(x) * 0.70710678118654752f;
     const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);      // v_rcp_f32 (1 ulp); __frcp_rn expands to a 12-instruction IEEE division
