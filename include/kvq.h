@@ -402,7 +402,8 @@ int kvq_gemm_bf16_ce(const void* A, const void* B, const void* bias, void* C, in
 
 /* ---- fp8 (OCP e4m3fn) forward GEMMs: extension named by BASELINE.json configs[4]; the reference is f32 throughout -> off by default.
  *   y = x . W^T + b of a BERT linear (modeling_bert.py:139-352) as  (sat(x sx) . sat(W sw)^T) / (sx sw) + b,  s = 448 / amax|.|
- *   per tensor, computed in the same step from the tensor that is quantised (no amax history).  Backward stays bf16.
+ *   per tensor, computed in the same step from the tensor that is quantised (no amax history).  Backward stays bf16 (but see the
+ *   input-gradient option below: kvq_gemm_fp8_nt_ex).
  * kvq_fp8_quantize: one bf16 matrix [rows, cols] (row stride ld) -> dense fp8 [rows, cols]; amax, scale: device scalars (written).
  * kvq_fp8_quantize_segments: ranges [seg_off[s], +seg_n[s]) (elements; device arrays; multiples of 16) of one bf16 buffer ->
  *   the same ranges of an fp8 buffer, one amax / scale per range: all GEMM weights of the model in two launches.
@@ -446,6 +447,42 @@ int kvq_attn_fwd_fp8(const void* q, const void* k, const void* v, const int64_t*
                      void* out, float* lse, void* out_fp8, int ld8, float* fp8_state, void* stream);
 int kvq_gemm_fp8_nt_gelu(const void* A8, const void* B8, const float* scale_a, const float* scale_b, const void* bias, void* Hout, void* Aout,
                          void* Aout_fp8, int ld8, float* fp8_state, int M, int N, int K, int lda, int ldb, int ldc, void* stream);
+
+/* ---- fp8 input-gradient GEMMs (option, off by default): gx[N,K] = gy[N,M] . W[M,K] as the NT product of gy in OCP e5m2 (the
+ * range gradients need) and the byte-transposed e4m3 weight mirror W^T[K,M] -- same scale, no requantisation.
+ * Operand formats of the fp8 GEMM / the quantisation passes: */
+#define KVQ_FP8_E4M3 0       /* OCP e4m3fn, largest value 448 */
+#define KVQ_FP8_E5M2 1       /* OCP e5m2, largest value 57344 */
+/* kvq_gemm_fp8_nt_ex: C[M,N] bf16 (+)= (A8[M,K] . B8[N,K]^T) / (scale_a[0] scale_b[0]) + bias.  a_format: the format of A8
+ *   (KVQ_FP8_E4M3 | KVQ_FP8_E5M2); B8 is e4m3.  accumulate != 0: the product (+ bias), rounded to bf16, is added to the C that is
+ *   there, in f32, and rounded once more (the epilogue of kvq_gemm_bf16's accumulate).  Refusals as kvq_gemm_fp8_nt: K %% 128,
+ *   lda / ldb %% 16 (fp8 elements), M, N, ldc %% 8, 16-byte aligned operands.  a_format = KVQ_FP8_E4M3, accumulate = 0 launches the
+ *   kernel of kvq_gemm_fp8_nt (same bits). */
+int kvq_gemm_fp8_nt_ex(const void* A8, const void* B8, const float* scale_a, const float* scale_b, const void* bias, void* C,
+                       int M, int N, int K, int lda, int ldb, int ldc, int a_format, int accumulate, void* stream);
+/* The quantisation calls above with the target format as an argument (fmt = KVQ_FP8_E4M3: the bytes of the calls above);
+ * round to nearest even, saturating at the format's largest value, a NaN stays a NaN.  Rows may be strided (ld >= cols, cols and
+ * ld %% 8 == 0); rows of a multiple of 16 columns are written in 16-byte pieces.  Kernel launches only: all three can be captured.
+ *   kvq_fp8_quantize_fmt         : amax pass + quantise pass, scale = max(fmt) / amax of the tensor itself (amax, scale: written)
+ *   kvq_fp8_quantize_delayed_fmt : one pass with the record's scale, this tensor's amax left in the record's partials (the record
+ *                                  layout of kvq_fp8_quantize_delayed).  out_fp8 == NULL: only the amax is noted (calibration)
+ *   kvq_fp8_update_scales_fmt    : scale = max(fmt) / (amax * headroom) for nsites consecutive records of ONE format; a record
+ *                                  whose partials are all 0 keeps its scale; headroom 0 only clears */
+int kvq_fp8_quantize_fmt(const void* x_bf16, int64_t rows, int cols, int64_t ld, void* out_fp8, float* amax, float* scale, int fmt,
+                         void* stream);
+int kvq_fp8_quantize_delayed_fmt(const void* x_bf16, int64_t rows, int cols, int64_t ld, void* out_fp8, float* state, int fmt,
+                                 void* stream);
+int kvq_fp8_update_scales_fmt(float* state, int nsites, float headroom, int fmt, void* stream);
+/* Byte transpose of an fp8 matrix: dst8[c, r] = src8[r, c], src8 [rows, cols] with row stride ld_src, dst8 [cols, rows] with row
+ * stride ld_dst (bytes); rows, cols, ld_src, ld_dst multiples of 16, 16-byte aligned buffers that do not overlap.
+ * kvq_fp8_transpose_segments: nseg dense matrices in one launch -- segment s is [seg_rows[s], seg_cols[s]] at src8 + src_off[s]
+ *   and goes, transposed and dense, to dst8 + dst_off[s] (device arrays of int64).  EVERY table entry must be a multiple
+ *   of 16: the tables live on the device, the host cannot check them, and the result for any other entry is undefined (the
+ *   kernel stays inside the segments, but its 16-byte accesses are misaligned and the dense layout is wrong); max_tiles >= ceil(rows / 128) * ceil(cols / 128) of every
+ *   segment.  One launch for every weight of a model. */
+int kvq_fp8_transpose(const void* src8, int rows, int cols, int64_t ld_src, void* dst8, int64_t ld_dst, void* stream);
+int kvq_fp8_transpose_segments(const void* src8, void* dst8, const int64_t* src_off, const int64_t* seg_rows, const int64_t* seg_cols,
+                               const int64_t* dst_off, int nseg, int64_t max_tiles, void* stream);
 
 /* torch.optim.Adam step (models/shelgon3/main.py:91: lr, weight_decay (L2, coupled), amsgrad) on flat buffers.
  *   p, m, v [, vmax] f32; g grad_dtype (scaled by grad_scale first); shadow_bf16 (may be NULL) receives bf16(p_new).

@@ -185,6 +185,34 @@ __device__ __forceinline__ uint2 quant8(const uint4 r, float s) {
     return make_uint2((unsigned)lo, (unsigned)hi);
 }
 
+// The same for OCP e5m2 (largest value 57344): the format of the gradients in the fp8 input-gradient GEMMs.  FMT: KVQ_FP8_E4M3 /
+// KVQ_FP8_E5M2 (include/kvq.h); quant8_fmt<KVQ_FP8_E4M3> IS quant8.
+constexpr float FP8_MAX_E5M2 = 57344.0f;
+template <int FMT>
+__host__ __device__ constexpr float fp8_max_of() { return FMT == KVQ_FP8_E5M2 ? FP8_MAX_E5M2 : FP8_MAX; }
+
+template <int FMT>
+__device__ __forceinline__ uint2 quant8_fmt(const uint4 r, float s) {
+    if constexpr (FMT == KVQ_FP8_E4M3) {
+        return quant8(r, s);
+    } else {
+        const unsigned w[4] = {r.x, r.y, r.z, r.w};
+        float f[8];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float a = __uint_as_float(w[u] << 16) * s, b = __uint_as_float(w[u] & 0xffff0000u) * s;
+            f[2 * u] = a != a ? a : fminf(fmaxf(a, -FP8_MAX_E5M2), FP8_MAX_E5M2);          // (a NaN stays a NaN, as in quant8)
+            f[2 * u + 1] = b != b ? b : fminf(fmaxf(b, -FP8_MAX_E5M2), FP8_MAX_E5M2);
+        }
+        int lo = 0, hi = 0;
+        lo = __builtin_amdgcn_cvt_pk_bf8_f32(f[0], f[1], lo, false);
+        lo = __builtin_amdgcn_cvt_pk_bf8_f32(f[2], f[3], lo, true);
+        hi = __builtin_amdgcn_cvt_pk_bf8_f32(f[4], f[5], hi, false);
+        hi = __builtin_amdgcn_cvt_pk_bf8_f32(f[6], f[7], hi, true);
+        return make_uint2((unsigned)lo, (unsigned)hi);
+    }
+}
+
 // 4 values (already rounded to bf16) -> 4 fp8 bytes, as quant8 does it
 __device__ __forceinline__ unsigned quant4(f32x4 v, float s) {
     float f[4] = {v.x * s, v.y * s, v.z * s, v.w * s};

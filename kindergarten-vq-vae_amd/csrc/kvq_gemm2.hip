@@ -1053,7 +1053,9 @@ __device__ __forceinline__ i32x8 join(bf16x8 lo, bf16x8 hi) {
     return v;
 }
 
-template <class C>
+// AFMT: the format of the A operand (KVQ_FP8_E4M3 | KVQ_FP8_E5M2: the instruction's format codes 0 = fp8, 1 = bf8); B is e4m3.  The B
+// fragments are the instruction's FIRST source and the A fragments its second, so AFMT is the second of the two format immediates.
+template <class C, int AFMT = KVQ_FP8_E4M3>
 __device__ __forceinline__ void cluster8(f32x4 (&acc)[C::FA][C::FB], const Frags8<C>& f, Frags8<C>& fn, const char* nstage,
                                          int wm, int wn, int lane, Stager<C>& sg, int slot, bool pending) {
     constexpr int NM = C::FA * C::FB, NP = C::PPW, NSUB = NP + 1, NF = 2 * (C::FA + C::FB), RSUB = NSUB - 1;
@@ -1072,7 +1074,7 @@ __device__ __forceinline__ void cluster8(f32x4 (&acc)[C::FA][C::FB], const Frags
         for (int i = m0; i < m1; ++i) {
             const int mi = i / C::FB, ni = i % C::FB;
             acc[mi][ni] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(join<C>(f.b[0][ni], f.b[1][ni]), join<C>(f.a[0][mi], f.a[1][mi]),
-                                                                            acc[mi][ni], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+                                                                            acc[mi][ni], 0, AFMT, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
         }
 #pragma unroll
         for (int i = m0; i < m1; ++i) {
@@ -1088,7 +1090,7 @@ __device__ __forceinline__ void cluster8(f32x4 (&acc)[C::FA][C::FB], const Frags
     __builtin_amdgcn_s_setprio(0);
 }
 
-template <class C, int EPI = EPI_NONE>
+template <class C, int EPI = EPI_NONE, int AFMT = KVQ_FP8_E4M3>
 __global__ __launch_bounds__(C::THREADS, C::MINW) void gemm2_f8_kernel(Params P) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1143,8 +1145,8 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void gemm2_f8_kernel(Params P)
                     pending = k + C::NS < nkt;
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if (half == 0) cluster8<C>(acc, f0, f1, smem + nslot * C::STAGE, wm, wn, lane, sg, slot, pending);
-                else cluster8<C>(acc, f1, f0, smem + nslot * C::STAGE, wm, wn, lane, sg, slot, pending);
+                if (half == 0) cluster8<C, AFMT>(acc, f0, f1, smem + nslot * C::STAGE, wm, wn, lane, sg, slot, pending);
+                else cluster8<C, AFMT>(acc, f1, f0, smem + nslot * C::STAGE, wm, wn, lane, sg, slot, pending);
                 if (pending) sg.advance();
                 __builtin_amdgcn_sched_barrier(0);
                 slot = nslot;
@@ -1307,6 +1309,48 @@ static int build_params(const kvq_gemm_problem* probs, int nprob, int layout, in
     return KVQ_OK;
 }
 
+// AFMT = KVQ_FP8_E4M3, accumulate = 0: kvq_gemm_fp8_nt.  accumulate: the EPI_NONE epilogue's C += (the bf16 kernel's), unchanged.
+template <int AFMT>
+static int gemm_fp8_nt_impl(const void* A8, const void* B8, const float* scale_a, const float* scale_b, const void* bias, void* C, int M, int N,
+                            int K, int lda, int ldb, int ldc, int accumulate, void* stream, const char* who) {
+    KVQ_REQUIRE(scale_a && scale_b, "%s: null scale pointer", who);
+    KVQ_REQUIRE(K > 0 && K % 128 == 0 && lda % 16 == 0 && ldb % 16 == 0, "%s: K %% 128 == 0 and lda, ldb %% 16 == 0 (fp8 elements)", who);
+    kvq_gemm_problem q;                         // the ring moves bytes: an fp8 row of K elements is a bf16 row of K / 2
+    q.A = A8; q.B = B8; q.C = C; q.bias = bias; q.M = M; q.N = N; q.K = K / 2; q.lda = lda / 2; q.ldb = ldb / 2; q.ldc = ldc;
+    q.accumulate = accumulate != 0;
+    g2::Params P;
+    // Tile (round 5): 128 x 256 unless that leaves CUs without a tile and 128 x 192 does not -- an [8192, 768] output is 192 tiles of
+    // the first and 256 of the second (KVQ_FP8_TILE=0: always 128 x 256, the rounds 2 - 4 behaviour; A/B switch)
+    static const bool narrow_ok = !(getenv("KVQ_FP8_TILE") && atoi(getenv("KVQ_FP8_TILE")) == 0);
+    const int t256 = ((M + 127) / 128) * ((N + 255) / 256), t192 = ((M + 127) / 128) * ((N + 191) / 192);
+    const bool narrow = narrow_ok && t256 < g2::persistent_grid() && t192 > t256;
+    if (int rc = build_params(&q, 1, KVQ_GEMM_NT, narrow ? KVQ_GEMM_TILE_128x192 : KVQ_GEMM_TILE_128x256, P, who)) return rc;
+    for (int i = 0; i < g2::MAX_PROBLEMS; ++i) { P.p[i].scaleA = scale_a; P.p[i].scaleB = scale_b; }
+    hipStream_t st = (hipStream_t)stream;
+    if (narrow) {
+        typedef g2::Cfg128x192<true, true> Cn;
+        static std::atomic<bool> attr_n{false};
+        if (!attr_n) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&g2::gemm2_f8_kernel<Cn, g2::EPI_NONE, AFMT>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, Cn::LDS);
+            if (e != hipSuccess) return fail(KVQ_E_LAUNCH, "hipFuncSetAttribute(gemm2_f8 128x192): %s", hipGetErrorString(e));
+            attr_n = true;
+        }
+        hipLaunchKernelGGL((g2::gemm2_f8_kernel<Cn, g2::EPI_NONE, AFMT>), dim3((unsigned)P.ntiles), dim3(Cn::THREADS), Cn::LDS, st, P);
+        return check_launch("gemm2_f8_kernel<128x192>");
+    }
+    typedef g2::Cfg128x256<true, true> Cf;
+    static std::atomic<bool> attr_done{false};
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&g2::gemm2_f8_kernel<Cf, g2::EPI_NONE, AFMT>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS);
+        if (e != hipSuccess) return fail(KVQ_E_LAUNCH, "hipFuncSetAttribute(gemm2_f8): %s", hipGetErrorString(e));
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((g2::gemm2_f8_kernel<Cf, g2::EPI_NONE, AFMT>), dim3((unsigned)P.ntiles), dim3(Cf::THREADS), Cf::LDS, st, P);
+    return check_launch("gemm2_f8_kernel");
+}
+
 extern "C" {
 
 #ifdef KVQ_G2_DIAG
@@ -1404,39 +1448,16 @@ int kvq_gemm_bf16_ce(const void* A, const void* B, const void* bias, void* Cout,
 
 int kvq_gemm_fp8_nt(const void* A8, const void* B8, const float* scale_a, const float* scale_b, const void* bias, void* C, int M, int N,
                     int K, int lda, int ldb, int ldc, void* stream) {
-    KVQ_REQUIRE(scale_a && scale_b, "kvq_gemm_fp8_nt: null scale pointer");
-    KVQ_REQUIRE(K > 0 && K % 128 == 0 && lda % 16 == 0 && ldb % 16 == 0, "kvq_gemm_fp8_nt: K %% 128 == 0 and lda, ldb %% 16 == 0 (fp8 elements)");
-    kvq_gemm_problem q;                         // the ring moves bytes: an fp8 row of K elements is a bf16 row of K / 2
-    q.A = A8; q.B = B8; q.C = C; q.bias = bias; q.M = M; q.N = N; q.K = K / 2; q.lda = lda / 2; q.ldb = ldb / 2; q.ldc = ldc; q.accumulate = 0;
-    g2::Params P;
-    // Tile (round 5): 128 x 256 unless that leaves CUs without a tile and 128 x 192 does not -- an [8192, 768] output is 192 tiles of
-    // the first and 256 of the second (KVQ_FP8_TILE=0: always 128 x 256, the rounds 2 - 4 behaviour; A/B switch)
-    static const bool narrow_ok = !(getenv("KVQ_FP8_TILE") && atoi(getenv("KVQ_FP8_TILE")) == 0);
-    const int t256 = ((M + 127) / 128) * ((N + 255) / 256), t192 = ((M + 127) / 128) * ((N + 191) / 192);
-    const bool narrow = narrow_ok && t256 < g2::persistent_grid() && t192 > t256;
-    if (int rc = build_params(&q, 1, KVQ_GEMM_NT, narrow ? KVQ_GEMM_TILE_128x192 : KVQ_GEMM_TILE_128x256, P, "kvq_gemm_fp8_nt")) return rc;
-    for (int i = 0; i < g2::MAX_PROBLEMS; ++i) { P.p[i].scaleA = scale_a; P.p[i].scaleB = scale_b; }
-    hipStream_t st = (hipStream_t)stream;
-    if (narrow) {
-        typedef g2::Cfg128x192<true, true> Cn;
-        static std::atomic<bool> attr_n{false};
-        if (!attr_n) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&g2::gemm2_f8_kernel<Cn>), hipFuncAttributeMaxDynamicSharedMemorySize, Cn::LDS);
-            if (e != hipSuccess) return fail(KVQ_E_LAUNCH, "hipFuncSetAttribute(gemm2_f8 128x192): %s", hipGetErrorString(e));
-            attr_n = true;
-        }
-        hipLaunchKernelGGL((g2::gemm2_f8_kernel<Cn>), dim3((unsigned)P.ntiles), dim3(Cn::THREADS), Cn::LDS, st, P);
-        return check_launch("gemm2_f8_kernel<128x192>");
-    }
-    typedef g2::Cfg128x256<true, true> Cf;
-    static std::atomic<bool> attr_done{false};
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&g2::gemm2_f8_kernel<Cf>), hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS);
-        if (e != hipSuccess) return fail(KVQ_E_LAUNCH, "hipFuncSetAttribute(gemm2_f8): %s", hipGetErrorString(e));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((g2::gemm2_f8_kernel<Cf>), dim3((unsigned)P.ntiles), dim3(Cf::THREADS), Cf::LDS, st, P);
-    return check_launch("gemm2_f8_kernel");
+    return gemm_fp8_nt_impl<KVQ_FP8_E4M3>(A8, B8, scale_a, scale_b, bias, C, M, N, K, lda, ldb, ldc, 0, stream, "kvq_gemm_fp8_nt");
+}
+
+int kvq_gemm_fp8_nt_ex(const void* A8, const void* B8, const float* scale_a, const float* scale_b, const void* bias, void* C,
+                       int M, int N, int K, int lda, int ldb, int ldc, int a_format, int accumulate, void* stream) {
+    KVQ_REQUIRE(a_format == KVQ_FP8_E4M3 || a_format == KVQ_FP8_E5M2, "kvq_gemm_fp8_nt_ex: a_format must be KVQ_FP8_E4M3 or KVQ_FP8_E5M2, got %d",
+                a_format);
+    if (a_format == KVQ_FP8_E5M2)
+        return gemm_fp8_nt_impl<KVQ_FP8_E5M2>(A8, B8, scale_a, scale_b, bias, C, M, N, K, lda, ldb, ldc, accumulate, stream, "kvq_gemm_fp8_nt_ex");
+    return gemm_fp8_nt_impl<KVQ_FP8_E4M3>(A8, B8, scale_a, scale_b, bias, C, M, N, K, lda, ldb, ldc, accumulate, stream, "kvq_gemm_fp8_nt_ex");
 }
 
 int kvq_gemm_fp8_nt_gelu(const void* A8, const void* B8, const float* scale_a, const float* scale_b, const void* bias, void* Hout, void* Aout,

@@ -33,6 +33,7 @@ class GemmProblem(C.Structure):
 
 
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
+FP8_E4M3, FP8_E5M2 = 0, 1                 # KVQ_FP8_E4M3 / KVQ_FP8_E5M2: operand formats of the fp8 GEMM and the quantisation passes
 GEMM_TILE_128x192, GEMM_TILE_128x256, GEMM_TILE_256x192, GEMM_TILE_256x256, GEMM_TILE_64x128 = 0, 1, 2, 3, 4
 
 # name -> (restype, argtypes); mirrors include/kvq.h line by line
@@ -105,6 +106,12 @@ SIGNATURES = {
     "kvq_adam_step_dev_fp8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]),
     "kvq_fp8_quantize_segments_periodic": (_int, [_vp, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _int, _vp]),
     "kvq_gemm_fp8_nt": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
+    "kvq_gemm_fp8_nt_ex": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _vp]),
+    "kvq_fp8_quantize_fmt": (_int, [_vp, _i64, _int, _i64, _vp, _vp, _vp, _int, _vp]),
+    "kvq_fp8_quantize_delayed_fmt": (_int, [_vp, _i64, _int, _i64, _vp, _vp, _int, _vp]),
+    "kvq_fp8_update_scales_fmt": (_int, [_vp, _int, _f32, _int, _vp]),
+    "kvq_fp8_transpose": (_int, [_vp, _int, _int, _i64, _vp, _i64, _vp]),
+    "kvq_fp8_transpose_segments": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _vp]),
     "kvq_dropout_residual_ln_fwd_fp8": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _f32, _f32, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kvq_attn_fwd_fp8_ok": (_int, [_int, _int]),
     "kvq_attn_fwd_fp8": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _int, _int, _f32, _f32,

@@ -34,7 +34,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import nnops
-from ._ffi import KvqError, check, io_dtype_of, lib, stream_ptr
+from ._ffi import FP8_E5M2, KvqError, check, io_dtype_of, lib, stream_ptr
 from .functional import _workspace
 
 V_ALIGN = 64   # vocabulary rows of the LM head are padded so logits rows are 128-byte aligned
@@ -290,6 +290,7 @@ class _StepGraphs:
                     eng._prepared = dict(enc=self.sorted, dec=self.dec[2:4] if self.dec else None)
                     dkw = dict(dec_ids=self.dec[0], dec_mask=self.dec[1], target_ids=self.dec[4]) if self.dec else {}
                     self.out = eng.forward_backward(self.ids, self.mask, training=eng.model.training, compute_grads=True, **dkw)
+                    self.fp8_bwd = (eng.fp8_bwd_launches, list(eng.fp8_bwd_sites))      # what THIS chain holds: restored by every replay
                     eng.optimizer_step()
                     self.graphs[-1].capture_end()
                     ok = True
@@ -332,6 +333,7 @@ class _StepGraphs:
 
     def run(self, ids, mask, prep, dec=None):
         """prep: TrainEngine._normalise_prepared()'s dict (pack = the whole batch as one tensor, or the sorted ids of either side)."""
+        self.eng.fp8_bwd_launches, self.eng.fp8_bwd_sites = self.fp8_bwd[0], list(self.fp8_bwd[1])
         if prep["pack"] is not None:
             self.pack.copy_(prep["pack"])           # a batch packed where it was built (TrainEngine.pack_batch): one copy
         else:                                       # otherwise the sort happens here -- outside the graphs, but in the step
@@ -369,7 +371,7 @@ class _StepGraphs:
 class TrainEngine:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
                  milestones=None, gamma=0.1, loss_recon_scale=1.0, loss_vq_scale=1.0, seed=1234,
-                 bucket_mib=64, process_group=None, fp8_forward=None):
+                 bucket_mib=64, process_group=None, fp8_forward=None, fp8_backward=None):
         self.model = model
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -557,6 +559,26 @@ class TrainEngine:
         self._fp8_fused = fp8_forward == "fused"
         self._fp8_all = fp8_forward in ("all", "fused")
         self._x8 = {}                      # data_ptr of a bf16 activation -> its fp8 copy, left by the producer for ONE fp8 GEMM
+        # option, off by default: input-gradient GEMMs gx = gy . W of the training step on the fp8 matrix cores --
+        # gy quantised to e5m2 by a delayed-scaling pass, against the byte-transposed e4m3 weight mirror (_w8t).  None: KVQ_FP8_BACKWARD
+        # from the environment, as fp8_forward reads KVQ_FP8 (bench.py --fp8 measures both arms that way; unset = off; it is ignored
+        # on an engine without fp8 forward GEMMs).  None is the DEFAULT: with KVQ_FP8_BACKWARD=1 in the environment every engine with
+        # fp8 forward GEMMs that does not pass False takes the option, and its backward bits change; pass False to rule that out.  Needs fp8 forward GEMMs, theirs is the weight mirror: an explicit True without
+        # them is refused.
+        if fp8_backward is None:
+            fp8_backward = self.fp8 and os.environ.get("KVQ_FP8_BACKWARD", "0") == "1"
+        if fp8_backward not in (False, True):
+            raise KvqError(f"TrainEngine: fp8_backward must be False, True or None (KVQ_FP8_BACKWARD), got {fp8_backward!r}")
+        self.fp8_backward = bool(fp8_backward)
+        if self.fp8_backward and not self.fp8:
+            raise KvqError("TrainEngine: fp8_backward needs fp8 forward GEMMs (fp8_forward / KVQ_FP8): the input-gradient GEMMs read "
+                           "the transposed copy of the forward's e4m3 weight mirror")
+        # fp8 input-gradient GEMMs of the last training step and their weight keys in launch order: counted while the step is
+        # scheduled (eagerly, or at capture -- a replay restores the counts of the graphs it replays)
+        self.fp8_bwd_launches = 0
+        self.fp8_bwd_sites = []
+        self._bwd8_mode = None             # "calibrate" | "run" while a training step's backward is scheduled
+        self._g8_index, self._g8_live, self._g8_ready, self._w8t = {}, set(), False, None
         if self.fp8:
             if self.dtype != torch.bfloat16:
                 raise KvqError("TrainEngine: fp8 forward GEMMs need the bf16 compute dtype")
@@ -669,12 +691,120 @@ class TrainEngine:
         self._w8_span = torch.from_numpy(fp8_span_table(offs, ns, fl.n)).to(self.dev)
         self._w8_amax = torch.zeros(len(keys), dtype=torch.float32, device=self.dev)
         self._w8_scale = torch.ones(len(keys), dtype=torch.float32, device=self.dev)
+        if self.fp8_backward:
+            self._fp8_bwd_setup(keys, offs, ns)
         self._fp8_quantize_weights()
         # activations: one {scale, amax} pair per GEMM input of the step, in call order (delayed scaling: include/kvq.h)
         self._a8_sites = len(keys)                    # one record per fp8 GEMM = per weight key (each is used once per forward)
         st = torch.zeros((self._a8_sites, lib().kvq_fp8_state_floats()), dtype=torch.float32, device=self.dev)
         st[:, 0] = 1.0
         self._a8_state = st
+
+    # ---- fp8 input-gradient GEMMs (option fp8_backward) ---------------------------------------------------------------------
+    _FP8_BWD_HEADROOM = 4.0       # as the forward sites: scale = max(e5m2) / (4 amax of the previous step)
+
+    def _fp8_bwd_setup(self, keys, offs, ns):
+        """The sites: every weight W [M, K] with a forward fp8 segment whose input gradient gx[N, K] = gy[N, M] . W can run as the NT
+        product gy8 . (W^T8)^T of the fp8 kernel -- the contraction M a multiple of 128 (the LM head's 30528 = 238.5 x 128 is not:
+        it stays bf16), K a multiple of 16.  Per site: the segment of the transposed mirror _w8t (dense, [K, M]; rebuilt from _w8
+        by ONE segmented transpose wherever _w8 changes) and one delayed-scaling record for gy in e5m2, scale 0 = not calibrated.
+        Which of these sites the backward really visits depends on the batch (BertOutput's input gradient is folded into the
+        GELU' GEMM at the shapes where that tile exists, and never comes here): the table starts with every candidate, and after
+        the calibration step the per-step transpose is cut down to the sites that are live (_fp8_bwd_end)."""
+        fl = self.flat
+        only = os.environ.get("KVQ_FP8_BWD_ONLY")        # diagnostic: restrict the sites to weights whose name contains one of these
+        sites, doff = [], 0
+        for key, o, n in zip(keys, offs, ns):
+            K = fl.seg[key][2][1]
+            M = n // K
+            if M * K != n or M % 128 or K % 16 or (only and not any(t in key for t in only.split(","))):
+                continue
+            sites.append((key, o, M, K, doff))
+            doff += n
+        if not sites:
+            raise KvqError("TrainEngine: fp8_backward asked for, but no weight with an fp8 forward segment has an eligible input "
+                           "gradient (contraction length a multiple of 128)" + (f"; KVQ_FP8_BWD_ONLY={only}" if only else ""))
+        assert all(o % 16 == 0 and d % 16 == 0 and M % 16 == 0 and K % 16 == 0 for _, o, M, K, d in sites)
+        self._g8_index = {key: i for i, (key, *_) in enumerate(sites)}
+        self._w8t_seg = {key: (d, M, K) for key, _, M, K, d in sites}
+        self._w8t = torch.zeros(doff, dtype=torch.uint8, device=self.dev)
+        self._w8t_sites = sites
+        self._fp8_transpose_table(sites)
+        self._g8_state = torch.zeros((len(sites), lib().kvq_fp8_state_floats()), dtype=torch.float32, device=self.dev)
+
+    def _fp8_transpose_table(self, sites):
+        """The device tables of the per-step segmented transpose for these sites (none: no launch)."""
+        t64 = lambda v: torch.tensor(v, dtype=torch.int64, device=self.dev)
+        self._w8t_tab = (t64([o for _, o, _, _, _ in sites]), t64([M for _, _, M, _, _ in sites]), t64([K for _, _, _, K, _ in sites]),
+                         t64([d for *_, d in sites])) if sites else None
+        self._w8t_tiles = max((-(-M // 128) * -(-K // 128) for _, _, M, K, _ in sites), default=0)
+
+    def _fp8_transpose_weights(self):
+        if self._w8t_tab is not None:
+            nnops.fp8_transpose_segments(self._w8, self._w8t, *self._w8t_tab, self._w8t_tiles)
+
+    def _fp8_bwd_begin(self, compute_grads):
+        """Start of a forward_backward call: what its backward does at an eligible site.  The FIRST training step of the engine
+        calibrates: every input gradient runs on bf16 and each site only notes the amax of its gy (a delayed scale of 1 would flush
+        gradients, whose magnitudes sit near e5m2's smallest subnormal, to zero -- nothing is quantised with a scale that does not
+        come from a measured amax of that site).  It is eager (train_step defers the capture): the scales are read back after it."""
+        self._bwd8_mode = None
+        if not (self.fp8_backward and compute_grads):
+            return
+        self.fp8_bwd_launches, self.fp8_bwd_sites = 0, []
+        if self._g8_ready:
+            self._bwd8_mode = "run"
+            return
+        if self._cap is not None or torch.cuda.is_current_stream_capturing():
+            raise KvqError("TrainEngine: the calibration step of fp8_backward (the first training step) cannot be captured")
+        self._bwd8_mode = "calibrate"
+
+    def _fp8_bwd_end(self):
+        """End of a training step's backward: next step's gradient scales from this step's amax (kernel; captured with the step).
+        After the calibration step: the sites whose amax was 0 -- a frozen branch, or a batch the site was not eligible at -- keep
+        scale 0 and stay on bf16."""
+        mode, self._bwd8_mode = self._bwd8_mode, None
+        if mode is None:
+            return
+        check(lib().kvq_fp8_update_scales_fmt(self._g8_state.data_ptr(), len(self._g8_index), self._FP8_BWD_HEADROOM, FP8_E5M2, stream_ptr()),
+              "kvq_fp8_update_scales_fmt")
+        if mode == "calibrate":
+            sc = self._g8_state[:, 0].cpu()
+            self._g8_live = {k for k, i in self._g8_index.items() if float(sc[i]) > 0.0 and bool(torch.isfinite(sc[i]))}
+            self._g8_ready = True
+            # from here on only the live sites' weights are transposed every step (the others' segments of _w8t are never read)
+            self._fp8_transpose_table([t for t in self._w8t_sites if t[0] in self._g8_live])
+            if not self._g8_live:
+                import sys
+                print("[kvq] fp8_backward: the calibration step (the first training step) left no input-gradient site with a measured "
+                      "amax -- a batch of fewer than 256 tokens, or every branch frozen; all input gradients of this engine stay on "
+                      "bf16", file=sys.stderr, flush=True)
+
+    def _dgrad_fp8(self, gy, key, out=None):
+        """gx = gy . W (added to `out` when given) on the fp8 matrix cores, or None where this product stays on the bf16 kernel: the
+        key has no site, gy has fewer than 256 rows or a contraction length that is no multiple of 128, strides that are not unit /
+        16-byte aligned, an uncalibrated or frozen site, the calibration step (which notes gy's amax here)."""
+        if self._bwd8_mode is None or key not in self._g8_index:
+            return None
+        if gy.dtype != torch.bfloat16 or gy.dim() != 2 or gy.shape[0] < 256 or gy.shape[1] % 128 or gy.stride(1) != 1 or gy.stride(0) % 8 \
+                or gy.data_ptr() % 16:
+            return None
+        d, M, K = self._w8t_seg[key]
+        if gy.shape[1] != M or (out is not None and (out.dtype != torch.bfloat16 or out.shape != (gy.shape[0], K) or out.stride(1) != 1
+                                                     or out.stride(0) % 8 or out.data_ptr() % 16)):
+            return None
+        st = self._g8_state[self._g8_index[key]]
+        if self._bwd8_mode == "calibrate":
+            nnops.fp8_quantize_delayed(gy, st, FP8_E5M2, amax_only=True)
+            return None
+        if key not in self._g8_live:
+            return None
+        g8 = nnops.fp8_quantize_delayed(gy, st, FP8_E5M2)
+        Wt8 = self._w8t[d:d + M * K].view(K, M)
+        self.fp8_bwd_launches += 1
+        self.fp8_bwd_sites.append(key)
+        return nnops.gemm_fp8_nt(g8, Wt8, st[0:], self._w8_scale[self._w8_index[key]:], out=out, a_format=FP8_E5M2,
+                                 accumulate=out is not None)
 
     def _a8_state_of(self, key):
         """The delayed-scaling record of the fp8 GEMM with weight `key` (its input's scale and amax partials)."""
@@ -696,10 +826,12 @@ class TrainEngine:
                                                            len(self._w8_index), self._w8_max, self._w8.data_ptr(), self._w8_amax.data_ptr(),
                                                            self._w8_scale.data_ptr(), self._state.data_ptr(), per, stream_ptr()),
                   "kvq_fp8_quantize_segments_periodic")
-            return
-        check(lib().kvq_fp8_quantize_segments(self.flat.shadow.data_ptr(), self._w8_off.data_ptr(), self._w8_n.data_ptr(), len(self._w8_index),
-                                              self._w8_max, self._w8.data_ptr(), self._w8_amax.data_ptr(), self._w8_scale.data_ptr(),
-                                              stream_ptr()), "kvq_fp8_quantize_segments")
+        else:
+            check(lib().kvq_fp8_quantize_segments(self.flat.shadow.data_ptr(), self._w8_off.data_ptr(), self._w8_n.data_ptr(),
+                                                  len(self._w8_index), self._w8_max, self._w8.data_ptr(), self._w8_amax.data_ptr(),
+                                                  self._w8_scale.data_ptr(), stream_ptr()), "kvq_fp8_quantize_segments")
+        if self._w8t is not None:          # the mirror changed (here, or in the Adam kernel just before): so does its transposed copy
+            self._fp8_transpose_weights()
 
     def _linear_fp8(self, x, W, b, key):
         si = self._w8_index[key]
@@ -896,13 +1028,19 @@ class TrainEngine:
             self._wgrad(gy, x, gW)
         if fl.trainable[bnames[0]] and not bias_done:     # bias_done: the LayerNorm backward kernel already produced it
             self._defer_colsum(gy, gb)
+        if not need_gx and gx_accum is None:
+            return None
+        gx = self._dgrad_fp8(gy, wnames[0], out=gx_accum)         # (the key of the weight's fp8 segment, as in _linear)
+        if gx is not None:
+            return gx
         if gx_accum is not None:
             return self._gemm(gy, W, "nn", out=gx_accum, accumulate=True)
-        return self._gemm(gy, W, "nn") if need_gx else None
-
-    def _dgrad(self, gy, W):
-        """gx = gy . W for a gradient that is not paired with a weight / bias gradient here (LM head, batched cross-K/V)."""
         return self._gemm(gy, W, "nn")
+
+    def _dgrad(self, gy, W, key=None):
+        """gx = gy . W for a gradient that is not paired with a weight / bias gradient here (LM head, batched cross-K/V)."""
+        gx = self._dgrad_fp8(gy, key) if key is not None else None
+        return gx if gx is not None else self._gemm(gy, W, "nn")
 
     # ------------------------------------------------------------------------------------------------------------
     # blocks: forward returns (output, saved); backward consumes saved
@@ -1227,6 +1365,7 @@ class TrainEngine:
             with torch.no_grad():            # the schedule IS the backward pass: no autograd graph over the few torch ops in it
                 if self.fp8:
                     self._x8.clear()
+                self._fp8_bwd_begin(compute_grads)
                 out = self._forward_backward(input_ids, attention_mask, training, compute_grads, dec_ids, dec_mask, want_logits,
                                              defer=bool(defer_backward), target_ids=target_ids, latents=latents,
                                              stop_after_encoder=bool(stop_after_encoder), skip_quantizer=bool(skip_quantizer),
@@ -1234,6 +1373,7 @@ class TrainEngine:
                 if defer_backward:
                     out["_resume"] = dict(gen=out.pop("_gen"), sorted_ids=self._sorted, step=self._step_host,
                                           versions=self._versions())
+                self._fp8_bwd_end()
                 if self.fp8 and compute_grads:
                     # the next TRAINING step's activation scales from this step's amax (4x headroom).  A forward-only call
                     # (evaluation, Shelgon.forward) uses the scales as they are and leaves them alone: an eval batch must not
@@ -1244,6 +1384,7 @@ class TrainEngine:
                     check(lib().kvq_fp8_update_scales(self._a8_state.data_ptr(), self._a8_sites, 0.0, stream_ptr()), "kvq_fp8_update_scales")
                 return out
         finally:
+            self._bwd8_mode = None
             nnops.set_seed_offset(None)
 
     def forward_logits(self, enc_ids, enc_mask, dec_ids=None, dec_mask=None, training=False, quantizer_training=None):
@@ -1643,7 +1784,7 @@ class TrainEngine:
                 self._defer_colsum(g_logits, fl.g("head.bias", rows=self.Vp))
         if tr["dec.emb.word"]:
             self._wgrad(g_logits, hN, fl.g("dec.emb.word", rows=self.Vp))            # [Vp,H] = g_logits^T hN
-        g_hN = self._dgrad(g_logits, Wv)
+        g_hN = self._dgrad(g_logits, Wv, key="dec.emb.word")      # (contracts over the padded vocabulary, 238.5 x 128: bf16)
         del logits, g_logits
         g_ta, _ = self._ln_bwd(g_hN, hpre, hmean, hrstd, fl.w32("head.ln.w"), 0.0, 0, 0,
                                g_gamma=fl.g("head.ln.w") if tr["head.ln.w"] else None,
@@ -1679,7 +1820,7 @@ class TrainEngine:
                 self._wgrad(g_kv_all, enc_out, fl.fused(self._cakv_w, fl.grad))
             if pb_kv_all is not None:
                 self._defer(pb_kv_all, fl.fused(self._cakv_b, fl.grad), B, pb_kv_all.shape[1], pb_kv_all.shape[1])
-            g_enc = self._dgrad(g_kv_all, fl.fused(self._cakv_w, fl.shadow))
+            g_enc = self._dgrad(g_kv_all, fl.fused(self._cakv_w, fl.shadow), key=self._cakv_w[0])
             del g_kv_all, kv_all
             self._grads_done_down_to(self._cakv_w[0])
         self._emb_bwd("dec.emb.", g_y, demb_saved, tied_accumulate=True)
@@ -2026,7 +2167,8 @@ class TrainEngine:
             return self._train_step_eager(input_ids, attention_mask, prep, dec)
         g = self._graphs.get(key)
         if g is None:
-            if seen < 2 or len(self._graphs) >= 4:      # warm the workspaces / GEMM plans eagerly first; few shapes only
+            # warm the workspaces / GEMM plans eagerly first; few shapes only; fp8_backward: its calibration step is eager
+            if seen < 2 or len(self._graphs) >= 4 or (self.fp8_backward and not self._g8_ready):
                 self._eager_seen[key] = seen + 1
                 return self._train_step_eager(input_ids, attention_mask, prep, dec)
             try:

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import torch
 
-from ._ffi import KvqError, check, io_dtype_of, lib, require_gpu, stream_ptr
+from ._ffi import FP8_E4M3, FP8_E5M2, KvqError, check, io_dtype_of, lib, require_gpu, stream_ptr
 from .functional import _workspace
 
 
@@ -657,26 +657,83 @@ def ce_forward_stats(logits, target, stats, row_loss, row_lse, pred, loss, acc):
                                      stream_ptr()), "kvq_ce_forward_stats")
 
 
-def fp8_quantize(x, out=None):
-    """bf16 [rows, cols] (unit column stride) -> (fp8 bytes [rows, cols] as uint8, scale [1] f32 on the device)."""
+FP8_FORMATS = {"e4m3": FP8_E4M3, "e5m2": FP8_E5M2, FP8_E4M3: FP8_E4M3, FP8_E5M2: FP8_E5M2}
+
+
+def _fp8_fmt(fmt):
+    if fmt not in FP8_FORMATS:
+        raise KvqError(f"fp8 format must be \"e4m3\" or \"e5m2\" (or _ffi.FP8_E4M3 / FP8_E5M2), got {fmt!r}")
+    return FP8_FORMATS[fmt]
+
+
+def fp8_quantize(x, out=None, fmt=None):
+    """bf16 [rows, cols] (unit column stride) -> (fp8 bytes [rows, cols] as uint8, scale [1] f32 on the device).  fmt: None = e4m3
+    through kvq_fp8_quantize (as before); "e4m3" / "e5m2": the format-taking entry kvq_fp8_quantize_fmt."""
     require_gpu(x)
     rows, cols = x.shape
     if out is None:
         out = torch.empty((rows, cols), dtype=torch.uint8, device=x.device)
     st = torch.empty(2, dtype=torch.float32, device=x.device)             # [amax, scale]
-    check(lib().kvq_fp8_quantize(x.data_ptr(), rows, cols, x.stride(0), out.data_ptr(), st[0:].data_ptr(), st[1:].data_ptr(), stream_ptr()),
-          "kvq_fp8_quantize")
+    if fmt is None:
+        check(lib().kvq_fp8_quantize(x.data_ptr(), rows, cols, x.stride(0), out.data_ptr(), st[0:].data_ptr(), st[1:].data_ptr(), stream_ptr()),
+              "kvq_fp8_quantize")
+    else:
+        check(lib().kvq_fp8_quantize_fmt(x.data_ptr(), rows, cols, x.stride(0), out.data_ptr(), st[0:].data_ptr(), st[1:].data_ptr(),
+                                         _fp8_fmt(fmt), stream_ptr()), "kvq_fp8_quantize_fmt")
     return out, st[1:]
 
 
-def gemm_fp8_nt(a8, b8, scale_a, scale_b, bias=None, out=None):
-    """out[M,N] bf16 = (a8[M,K] @ b8[N,K].T) / (scale_a * scale_b) + bias on the fp8 matrix cores."""
+def fp8_quantize_delayed(x, state, fmt, out=None, amax_only=False):
+    """One pass over bf16 x [rows, cols]: the fp8 bytes (format fmt) under the scale state[0] of the delayed-scaling record `state`,
+    this tensor's amax left in the record.  amax_only: nothing is written but the amax (returns None)."""
+    require_gpu(x, state)
+    rows, cols = x.shape
+    if out is None and not amax_only:
+        out = torch.empty((rows, cols), dtype=torch.uint8, device=x.device)
+    check(lib().kvq_fp8_quantize_delayed_fmt(x.data_ptr(), rows, cols, x.stride(0), None if amax_only else out.data_ptr(), state.data_ptr(),
+                                             _fp8_fmt(fmt), stream_ptr()), "kvq_fp8_quantize_delayed_fmt")
+    return None if amax_only else out
+
+
+def fp8_transpose(x8, out=None):
+    """The byte transpose of an fp8 matrix held as uint8 [rows, cols] (unit column stride; rows, cols and the row stride multiples
+    of 16): out [cols, rows] = x8.t(), dense."""
+    require_gpu(x8)
+    if x8.dim() != 2 or x8.element_size() != 1 or x8.stride(1) != 1:
+        raise KvqError("fp8_transpose: a 2-d one-byte tensor with unit column stride")
+    rows, cols = x8.shape
+    if out is None:
+        out = torch.empty((cols, rows), dtype=x8.dtype, device=x8.device)
+    check(lib().kvq_fp8_transpose(x8.data_ptr(), rows, cols, x8.stride(0), out.data_ptr(), out.stride(0), stream_ptr()), "kvq_fp8_transpose")
+    return out
+
+
+def fp8_transpose_segments(src8, dst8, src_off, rows, cols, dst_off, max_tiles):
+    """Dense fp8 matrices [rows[s], cols[s]] at src8 + src_off[s] -> their transposes at dst8 + dst_off[s], one launch (device int64
+    tables, every entry a multiple of 16; max_tiles >= ceil(rows / 128) * ceil(cols / 128) of every segment)."""
+    require_gpu(src8, dst8, src_off, rows, cols, dst_off)
+    check(lib().kvq_fp8_transpose_segments(src8.data_ptr(), dst8.data_ptr(), src_off.data_ptr(), rows.data_ptr(), cols.data_ptr(),
+                                           dst_off.data_ptr(), src_off.numel(), int(max_tiles), stream_ptr()), "kvq_fp8_transpose_segments")
+    return dst8
+
+
+def gemm_fp8_nt(a8, b8, scale_a, scale_b, bias=None, out=None, a_format=None, accumulate=False):
+    """out[M,N] bf16 (+)= (a8[M,K] @ b8[N,K].T) / (scale_a * scale_b) + bias on the fp8 matrix cores.  a_format None, accumulate False:
+    kvq_gemm_fp8_nt (both operands e4m3), as before; otherwise kvq_gemm_fp8_nt_ex with a8 in a_format ("e4m3" / "e5m2"; b8 is e4m3)
+    and, with accumulate, the product added to the `out` that is there."""
     M, K = a8.shape
     N = b8.shape[0]
+    if accumulate and out is None:
+        raise KvqError("gemm_fp8_nt: accumulate needs the output to add to")
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a8.device)
-    check(lib().kvq_gemm_fp8_nt(a8.data_ptr(), b8.data_ptr(), scale_a.data_ptr(), scale_b.data_ptr(), _p(bias), out.data_ptr(), M, N, K,
-                                a8.stride(0), b8.stride(0), out.stride(0), stream_ptr()), "kvq_gemm_fp8_nt")
+    if a_format is None and not accumulate:
+        check(lib().kvq_gemm_fp8_nt(a8.data_ptr(), b8.data_ptr(), scale_a.data_ptr(), scale_b.data_ptr(), _p(bias), out.data_ptr(), M, N, K,
+                                    a8.stride(0), b8.stride(0), out.stride(0), stream_ptr()), "kvq_gemm_fp8_nt")
+    else:
+        check(lib().kvq_gemm_fp8_nt_ex(a8.data_ptr(), b8.data_ptr(), scale_a.data_ptr(), scale_b.data_ptr(), _p(bias), out.data_ptr(), M, N, K,
+                                       a8.stride(0), b8.stride(0), out.stride(0), _fp8_fmt("e4m3" if a_format is None else a_format),
+                                       1 if accumulate else 0, stream_ptr()), "kvq_gemm_fp8_nt_ex")
     return out
 
 

@@ -90,7 +90,8 @@ def main():
         # scheduler tick and the RCCL gradient exchange; `opt` above is then only the reference-shaped handle in run_conf.json
         engine = TrainEngine(model, lr=LR, weight_decay=WEIGHT_DECAY, amsgrad=AMSGRAD,
                              milestones=MILESTONES if LR_SCHEDULER == "MultiStepLR" else None, gamma=GAMMA, bucket_mib=GRAD_BUCKET_MIB,
-                             fp8_forward=FP8_FORWARD if FP8_FORWARD else None)       # (None: the KVQ_FP8 environment switch decides)
+                             fp8_forward=FP8_FORWARD if FP8_FORWARD else None,       # (None: the KVQ_FP8 environment switch decides)
+                             fp8_backward=FP8_BACKWARD if FP8_BACKWARD else None)     # (None: KVQ_FP8_BACKWARD)
         if TOKEN_CACHE and same_tok:
             for c in caches:
                 c.packed_pad_id = engine.pad_idx if not any_perturb else "off"     # perturbed ids are sorted by the engine itself

@@ -34,6 +34,7 @@ MODEL_MODE = "full"                  # full | dec-head-ft | enc-head-ft-dec-head
 COMPUTE_DTYPE = "bfloat16"           # bfloat16 | float32
 USE_ENGINE = True                    # kvq.engine.TrainEngine (explicit fwd/bwd on flat buffers) when the model shape allows
 FP8_FORWARD = False                  # extension (BASELINE.json configs[4]): forward GEMMs on the fp8 matrix cores -- False | True | "wide" | "all"
+FP8_BACKWARD = False                 # option on top of FP8_FORWARD: input-gradient GEMMs on fp8 (e5m2 gradients, transposed e4m3 weights); DESIGN.md section 5
 
 VQ_MODE = "VectorQuantizer"          # VectorQuantizer | GumbelQuantizer | MultiVectorQuantizer (extension: VQ_N_FACTORS codebooks)
 VQ_N_FACTORS = 1                     # MultiVectorQuantizer: codebooks = slices of the encoder output (must divide VQ_E_DIM)
