@@ -504,6 +504,7 @@ int kvq_adam_step(float* p, const void* g, float* m, float* v, float* vmax, void
 /* ---- device-resident step state (hipGraph-friendly training step) ------------------------------------------------------
  * step_state: 24 bytes of device memory, zero-initialised = "no optimiser step applied yet":
  *     struct { uint64_t step; float lr, bc1, bc2s, pad; }
+ * (its optional companion, the 32-byte gradient guard state of a step that measures / clips its gradient norm: "gradient guard" below)
  * kvq_step_state_advance   one-thread kernel run at the start of an optimiser step: step += 1, lr = lr0 * gamma^(number of
  *                          milestones <= step-1)  (torch MultiStepLR ticked once per finished step, Trainer.py:114-115),
  *                          bc1 = 1 - beta1^step, bc2s = sqrt(1 - beta2^step).  At most 8 milestones (host array).
@@ -524,6 +525,39 @@ int kvq_dropout(const void* x, int64_t n, float p_drop, uint64_t seed, uint32_t 
 /* Zero 1..4 byte ranges (16-byte aligned pointers and sizes) in one launch: the word / position / token-type gradient tables of
  * BertEmbeddings (modeling_bert.py:53-58) before kvq_embed_grad and the batched reductions add into them. */
 int kvq_zero_ranges(void* const* ptrs, const int64_t* bytes, int n, void* stream);
+
+/* ---- gradient guard: global gradient norm, clipping by it, and the skip of a non-finite step (csrc/kvq_gradnorm.hip) ---------
+ * guard state: 32 bytes of device memory beside the step state, zero-initialised:
+ *     struct { double sumsq; float norm, coef; uint32_t skip, pad; uint64_t skipped; }
+ * Between backward and Adam a step runs, on its own stream and with no host round trip (so a captured step replays it unchanged):
+ * kvq_grad_sumsq_partials  P = 2048, the number of f64 partial sums one kvq_grad_sumsq_partial call writes.  A constant of the
+ *                          library, NOT derived from the device's CU count: the same buffer gives the same bits on every box.
+ * kvq_grad_sumsq_partial   partials[0..P) = partial sums of g[i]^2 over n >= 1 elements (grad_dtype KVQ_F32 / KVQ_BF16, g 16-byte
+ *                          aligned, n_partials must be P).  Deterministic: a fixed grid of P workgroups, elements [8c, 8c+8) go to
+ *                          thread c mod (256 P) of that grid, the last n %% 8 elements take a scalar path in thread 0; no float
+ *                          atomics.  The 8 squares of a 16-byte chunk are added in f32, everything above in f64.  One call per
+ *                          piece of the gradient, each into its own P slots of one partials buffer.
+ * kvq_grad_guard_finalize  one workgroup: sumsq = sum of the n_total partials (a multiple of P; thread t of 256 adds partials t,
+ *                          t + 256, ... in index order, then a fixed tree, all f64), norm = (float)sqrt(sumsq).  sumsq finite:
+ *                          coef = min(1, max_norm / (norm + 1e-6f)) (torch.nn.utils.clip_grad_norm_), skip = 0; max_norm = +inf
+ *                          gives coef = 1: measure and guard only.  sumsq inf or NaN (a non-finite gradient, or the overflow of
+ *                          an f32 square): coef = 0, skip = 1, skipped += 1.  sumsq, norm, coef and skip are written by every call.
+ * kvq_adam_step_guarded[_fp8]  kvq_adam_step_dev[_fp8] plus the guard state, read on the device: the gradient is scaled by
+ *                          grad_scale * guard->coef; with guard->skip set the kernel returns before its first store, so p, m, v,
+ *                          vmax, the bf16 shadow and the fp8 mirror keep their bits and neither weight decay nor the moment decays
+ *                          run.  (kvq_adam_step* pass no guard: their code path is unchanged.)
+ * A skipped step still runs kvq_step_state_advance: dropout masks and the learning-rate schedule move on, and bc1 / bc2s of the
+ * step state therefore count ATTEMPTED steps, not applied ones. */
+int kvq_grad_sumsq_partials(void);
+int kvq_grad_sumsq_partial(const void* g, int64_t n, int grad_dtype, double* partials, int n_partials, void* stream);
+int kvq_grad_guard_finalize(const double* partials, int n_total, float max_norm, void* guard, void* stream);
+int kvq_adam_step_guarded(float* p, const void* g, float* m, float* v, float* vmax, void* shadow_bf16, int64_t n, int grad_dtype,
+                          const void* step_state, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                          const void* guard, void* stream);
+int kvq_adam_step_guarded_fp8(float* p, const void* g, float* m, float* v, float* vmax, void* shadow_bf16, int64_t n, int grad_dtype,
+                              const void* step_state, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                              void* w8_mirror, const int* span_segment, const float* seg_scale, const int64_t* seg_off,
+                              const int64_t* seg_n, int nseg, int64_t first_element, const void* guard, void* stream);
 
 
 /* ---- the consumer of the code indices: word x code counts ------------------------------------------------------------------

@@ -249,6 +249,15 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
     return v;
 }
 
+// ---- gradient guard state (include/kvq.h): written by kvq_grad_guard_finalize (csrc/kvq_gradnorm.hip), read by adam_kernel -----
+struct GradGuard {
+    double sumsq;                 // sum of squares of the step's gradient
+    float norm, coef;             // sqrt(sumsq); what the Adam kernels multiply the gradient by (0 on a skipped step)
+    uint32_t skip, pad;           // 1: the gradient is not finite, the Adam kernels store nothing
+    unsigned long long skipped;   // steps skipped so far
+};
+static_assert(sizeof(GradGuard) == 32, "the guard state is 32 bytes (include/kvq.h)");
+
 // torch.argmin ordering: strictly smaller wins; NaN is smaller than any number; equal -> lower index.
 __device__ __forceinline__ bool dist_less(float d, float best) { return (d < best) || ((d != d) && (best == best)); }
 __device__ __forceinline__ bool dist_equal(float a, float b) { return (a == b) || ((a != a) && (b != b)); }

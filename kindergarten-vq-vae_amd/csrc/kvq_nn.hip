@@ -832,7 +832,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                     float* __restrict__ v, float* __restrict__ vmax,
                                                     unsigned short* __restrict__ shadow, int64_t n4, float lr, float b1,
                                                     float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                    float grad_scale, const float* __restrict__ hyper, int n_tail, AdamFp8 f8) {
+                                                    float grad_scale, const float* __restrict__ hyper, int n_tail, AdamFp8 f8,
+                                                    const GradGuard* __restrict__ guard) {
+    if (guard) {                                                           // kvq_adam_step_guarded*: the step's gradient guard (uniform)
+        if (guard->skip) return;                                           // non-finite gradient: nothing is stored, nothing decays
+        grad_scale *= guard->coef;                                         // the clipping coefficient of kvq_grad_guard_finalize
+    }
     if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2_sqrt = hyper[2]; }     // device-resident step state (kvq_step_state_advance)
     const int64_t n8 = n4 >> 1;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
@@ -2922,10 +2927,12 @@ int kvq_gelu_bwd(const void* h, const void* g_a, void* g_h, int64_t n, int io_dt
 
 static int adam_launch(float* p, const void* g, float* m, float* v, float* vmax, void* shadow_bf16, int64_t n, int grad_dtype,
                        float lr, float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2s, float grad_scale,
-                       const float* hyper, void* stream, AdamFp8 f8 = AdamFp8{}) {
+                       const float* hyper, void* stream, AdamFp8 f8 = AdamFp8{}, const void* guard = nullptr) {
     KVQ_REQUIRE(p && g && m && v && n > 0, "kvq_adam_step: bad argument");
     KVQ_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)vmax | (uintptr_t)shadow_bf16) & 15) == 0,
                 "kvq_adam_step: 16-byte aligned buffers required");
+    KVQ_REQUIRE(((uintptr_t)guard & 7) == 0, "kvq_adam_step: 8-byte aligned guard state required");
+    const GradGuard* gd = reinterpret_cast<const GradGuard*>(guard);
     const int64_t n4 = n / 4;
     const int n_tail = (int)(n - 4 * n4);
     const int64_t n8 = (n4 + 1) / 2;
@@ -2934,9 +2941,9 @@ static int adam_launch(float* p, const void* g, float* m, float* v, float* vmax,
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_DT(grad_dtype,
                 hipLaunchKernelGGL(adam_kernel<KVQ_F32>, dim3(blocks), dim3(256), 0, st, p, g, m, v, vmax, (unsigned short*)shadow_bf16, n4,
-                                   lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, hyper, n_tail, f8),
+                                   lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, hyper, n_tail, f8, gd),
                 hipLaunchKernelGGL(adam_kernel<KVQ_BF16>, dim3(blocks), dim3(256), 0, st, p, g, m, v, vmax, (unsigned short*)shadow_bf16, n4,
-                                   lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, hyper, n_tail, f8));
+                                   lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, hyper, n_tail, f8, gd));
     return check_launch("adam_kernel");
 }
 
@@ -2970,6 +2977,30 @@ int kvq_adam_step_dev_fp8(float* p, const void* g, float* m, float* v, float* vm
     f8.e_base = first_element;
     return adam_launch(p, g, m, v, vmax, shadow_bf16, n, grad_dtype, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale,
                        reinterpret_cast<const float*>(reinterpret_cast<const char*>(step_state) + 8), stream, f8);
+}
+
+// the two entry points above behind a gradient guard (csrc/kvq_gradnorm.hip): scale = grad_scale * guard->coef, nothing stored on a skip
+int kvq_adam_step_guarded(float* p, const void* g, float* m, float* v, float* vmax, void* shadow_bf16, int64_t n, int grad_dtype,
+                          const void* step_state, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                          const void* guard, void* stream) {
+    KVQ_REQUIRE(step_state && guard, "kvq_adam_step_guarded: null step state or guard state");
+    return adam_launch(p, g, m, v, vmax, shadow_bf16, n, grad_dtype, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale,
+                       reinterpret_cast<const float*>(reinterpret_cast<const char*>(step_state) + 8), stream, AdamFp8{}, guard);
+}
+
+int kvq_adam_step_guarded_fp8(float* p, const void* g, float* m, float* v, float* vmax, void* shadow_bf16, int64_t n, int grad_dtype,
+                              const void* step_state, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                              void* w8_mirror, const int* span_segment, const float* seg_scale, const int64_t* seg_off,
+                              const int64_t* seg_n, int nseg, int64_t first_element, const void* guard, void* stream) {
+    KVQ_REQUIRE(step_state && shadow_bf16 && guard, "kvq_adam_step_guarded_fp8: step state, bf16 shadow and guard state required");
+    KVQ_REQUIRE(w8_mirror && span_segment && seg_scale && seg_off && seg_n && nseg > 0, "kvq_adam_step_guarded_fp8: null fp8 argument");
+    KVQ_REQUIRE(first_element >= 0 && first_element % 8 == 0 && n % 8 == 0 && ((uintptr_t)w8_mirror & 7) == 0,
+                "kvq_adam_step_guarded_fp8: the range must start and end at multiples of 8 elements");
+    AdamFp8 f8;
+    f8.w8 = (unsigned char*)w8_mirror; f8.gseg = span_segment; f8.scale = seg_scale; f8.seg_off = seg_off; f8.seg_n = seg_n; f8.nseg = nseg;
+    f8.e_base = first_element;
+    return adam_launch(p, g, m, v, vmax, shadow_bf16, n, grad_dtype, 0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, grad_scale,
+                       reinterpret_cast<const float*>(reinterpret_cast<const char*>(step_state) + 8), stream, f8, guard);
 }
 
 int kvq_step_state_advance(void* step_state, float lr0, float gamma, const int64_t* milestones, int n_milestones, float beta1,

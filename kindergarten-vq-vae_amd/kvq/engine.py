@@ -185,6 +185,18 @@ class FlatParams:
             else:
                 self.ranges.append((o, e))
 
+        # the trainable PARAMETER elements as contiguous pieces: the ranges without the alignment padding behind an entry and the
+        # padded rows of the vocabulary table (what a global gradient norm runs over; every piece starts at a multiple of 16)
+        self.pieces: List[Tuple[int, int]] = []
+        for name, p, padded in entries:
+            if not p.requires_grad or p.numel() == 0:
+                continue
+            o, n, _ = self.seg[name]
+            if self.pieces and self.pieces[-1][1] == o:
+                self.pieces[-1] = (self.pieces[-1][0], o + n)
+            else:
+                self.pieces.append((o, o + n))
+
     def _lazy(self, attr, dtype):
         t = getattr(self, attr)
         if t is None:
@@ -293,6 +305,8 @@ class _StepGraphs:
                     self.fp8_bwd = (eng.fp8_bwd_launches, list(eng.fp8_bwd_sites))      # what THIS chain holds: restored by every replay
                     eng.optimizer_step()
                     self.graphs[-1].capture_end()
+                    if eng._guard is not None:      # grad_norm / grad_clip_coef: views of the guard state, run() hands out copies
+                        self.out.update(eng._guard_out)
                     ok = True
                 finally:
                     eng._cap = None
@@ -371,8 +385,9 @@ class _StepGraphs:
 class TrainEngine:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
                  milestones=None, gamma=0.1, loss_recon_scale=1.0, loss_vq_scale=1.0, seed=1234,
-                 bucket_mib=64, process_group=None, fp8_forward=None, fp8_backward=None):
+                 bucket_mib=64, process_group=None, fp8_forward=None, fp8_backward=None, max_grad_norm=None):
         self.model = model
+        self.max_grad_norm = self.check_max_grad_norm(max_grad_norm, env=True)     # (before anything is laid out: a bad value changes nothing)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise KvqError("TrainEngine needs the model on an MI355X (there is no CPU path)")
@@ -573,6 +588,17 @@ class TrainEngine:
         if self.fp8_backward and not self.fp8:
             raise KvqError("TrainEngine: fp8_backward needs fp8 forward GEMMs (fp8_forward / KVQ_FP8): the input-gradient GEMMs read "
                            "the transposed copy of the forward's e4m3 weight mirror")
+        # option, off by default: the step measures the global norm of its gradient between backward and Adam
+        # (kvq_grad_sumsq_partial / kvq_grad_guard_finalize), Adam scales the gradient by min(1, max_grad_norm / (norm + 1e-6)) --
+        # torch.nn.utils.clip_grad_norm_ -- and a step whose gradient is not finite stores nothing.  float("inf"): measure and
+        # guard, never clip.  None: KVQ_MAX_GRAD_NORM from the environment, as fp8_backward reads KVQ_FP8_BACKWARD; unset / empty: off.
+        # Off = no guard buffer, no launch added, today's Adam calls.
+        self._guard = self._gn_partials = None
+        if self.max_grad_norm is not None:
+            self._gn_P = nnops.grad_sumsq_partials()
+            self._guard = nnops.new_grad_guard(dev)
+            f = self._guard[1:2].view(torch.float32)
+            self._guard_out = dict(grad_norm=f[0], grad_clip_coef=f[1])      # views: train_step hands out copies
         # fp8 input-gradient GEMMs of the last training step and their weight keys in launch order: counted while the step is
         # scheduled (eagerly, or at capture -- a replay restores the counts of the graphs it replays)
         self.fp8_bwd_launches = 0
@@ -1975,6 +2001,60 @@ class TrainEngine:
         torch.sum(g_logits.float(), dim=0, out=self.g_pb)     # (out=: a same-dtype copy_ would be a memcpy NODE of a captured step)
         return self._mm(g_logits, Wp, "nn")
 
+    @staticmethod
+    def check_max_grad_norm(v, env=False):
+        """None (off), or the float > 0 / float("inf") a TrainEngine(max_grad_norm=...) accepts; anything else raises KvqError.
+        env: None means KVQ_MAX_GRAD_NORM from the environment (unset or empty: off)."""
+        if v is None and env and os.environ.get("KVQ_MAX_GRAD_NORM", "") != "":
+            try:
+                v = float(os.environ["KVQ_MAX_GRAD_NORM"])
+            except ValueError:
+                raise KvqError(f"TrainEngine: KVQ_MAX_GRAD_NORM (max_grad_norm) must be a float > 0 or inf, got "
+                               f"{os.environ['KVQ_MAX_GRAD_NORM']!r}") from None
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0:
+            raise KvqError(f"TrainEngine: max_grad_norm must be None, a float > 0 or float('inf'), got {v!r}")
+        return float(v)
+
+    @property
+    def skipped_steps(self):
+        """Optimiser steps skipped so far because their gradient was not finite (max_grad_norm only; synchronises)."""
+        return nnops.read_grad_guard(self._guard)["skipped"] if self._guard is not None else 0
+
+    def _gn_pieces(self, lo, hi):
+        """Sum-of-squares launches over the parameter elements of the flat gradient inside [lo, hi): one per contiguous piece, each
+        into the next kvq_grad_sumsq_partials() slots of the step's partials buffer."""
+        grad, P = self.flat.grad, self._gn_P
+        for (a, b) in self.flat.pieces:
+            a, b = max(a, lo), min(b, hi)
+            if a < b:
+                nnops.grad_sumsq_partial(grad[a:b], self._gn_partials[self._gn_slot * P:(self._gn_slot + 1) * P])
+                self._gn_slot += 1
+
+    def _gn_begin(self, cut):
+        """Size the partials buffer for this step's launches (the pieces, one more where `cut` splits one, the aux gradients)."""
+        fl = self.flat
+        n = sum(1 for (a, b) in fl.pieces if a < cut) + sum(1 for (a, b) in fl.pieces if b > cut) \
+            + sum(1 for x in self.aux if x["p"].requires_grad)
+        if n == 0:
+            raise KvqError("TrainEngine: max_grad_norm on a model without a trainable parameter")
+        if self._gn_partials is None or self._gn_partials.numel() != n * self._gn_P:
+            if self._cap is not None:
+                raise KvqError("TrainEngine: the gradient-norm partials buffer changed size inside a captured step")
+            self._gn_partials = torch.zeros(n * self._gn_P, dtype=torch.float64, device=self.dev)
+        self._gn_slot = 0
+
+    def _gn_finish(self):
+        """The aux gradients' partials, then the guard: norm, clipping coefficient, skip flag -- all on the device."""
+        P = self._gn_P
+        for x in self.aux:
+            if x["p"].requires_grad:
+                nnops.grad_sumsq_partial(x["g"].view(-1), self._gn_partials[self._gn_slot * P:(self._gn_slot + 1) * P])
+                self._gn_slot += 1
+        assert self._gn_slot * P == self._gn_partials.numel(), (self._gn_slot, self._gn_partials.numel())
+        nnops.grad_guard_finalize(self._gn_partials, self.max_grad_norm, self._guard)
+
     def _adam_ranges(self, lo, hi):
         fl = self.flat
         b1, b2 = self.betas
@@ -1984,16 +2064,19 @@ class TrainEngine:
                 if a % 8 or b % 8:           # (segments and chunk cuts are multiples of 16: cannot happen; a silent fallback would
                     raise KvqError(f"TrainEngine: Adam range [{a}, {b}) is not 8-aligned")       # leave the fp8 mirror stale)
                 # the update also writes the fp8 mirror of the GEMM weights in [a, b) (scales of the last refresh)
-                check(lib().kvq_adam_step_dev_fp8(fl.master[a:b].data_ptr(), fl.grad[a:b].data_ptr(), fl.m[a:b].data_ptr(), fl.v[a:b].data_ptr(),
-                                                  fl.vmax[a:b].data_ptr() if fl.vmax is not None else None, fl.shadow[a:b].data_ptr(), b - a,
-                                                  nnops.io_dtype_of(fl.grad), self._state.data_ptr(), b1, b2, self.eps, self.wd, 1.0,
-                                                  self._w8.data_ptr(), self._w8_span.data_ptr(), self._w8_scale.data_ptr(),
-                                                  self._w8_off.data_ptr(), self._w8_n.data_ptr(), len(self._w8_index), a, stream_ptr()),
-                      "kvq_adam_step_dev_fp8")
+                args = (fl.master[a:b].data_ptr(), fl.grad[a:b].data_ptr(), fl.m[a:b].data_ptr(), fl.v[a:b].data_ptr(),
+                        fl.vmax[a:b].data_ptr() if fl.vmax is not None else None, fl.shadow[a:b].data_ptr(), b - a,
+                        nnops.io_dtype_of(fl.grad), self._state.data_ptr(), b1, b2, self.eps, self.wd, 1.0,
+                        self._w8.data_ptr(), self._w8_span.data_ptr(), self._w8_scale.data_ptr(),
+                        self._w8_off.data_ptr(), self._w8_n.data_ptr(), len(self._w8_index), a)
+                if self._guard is not None:
+                    check(lib().kvq_adam_step_guarded_fp8(*args, self._guard.data_ptr(), stream_ptr()), "kvq_adam_step_guarded_fp8")
+                else:
+                    check(lib().kvq_adam_step_dev_fp8(*args, stream_ptr()), "kvq_adam_step_dev_fp8")
             elif a < b:
                 nnops.adam_step_dev(fl.master[a:b], fl.grad[a:b], fl.m[a:b], fl.v[a:b], self._state, b1, b2, self.eps, self.wd,
                                     vmax=fl.vmax[a:b] if fl.vmax is not None else None,
-                                    shadow=fl.shadow[a:b] if fl.shadow is not fl.master else None)
+                                    shadow=fl.shadow[a:b] if fl.shadow is not fl.master else None, guard=self._guard)
 
     def optimizer_step(self):
         fl = self.flat
@@ -2007,6 +2090,21 @@ class TrainEngine:
         if self.vq_ema:          # the codebook follows the EMA of its assigned encoder outputs (backward has used the old one by now)
             self._eager(self._ema_step)
         self._step_host += 1
+        if self._guard is not None:
+            # max_grad_norm: every Adam launch waits for the norm of the WHOLE (averaged) gradient.  Multi-GPU: the tail [cut, n) is
+            # reduced while the head is still being exchanged, the head, the aux gradients and the guard behind _exchange_tail -- Adam
+            # no longer overlaps the head's all-reduce.  A skipped step still advances the step state.
+            self._gn_begin(cut)
+            self._gn_pieces(cut, fl.n)
+            if self._dp:
+                self._eager(self._exchange_tail)
+                self._gn_pieces(0, cut)
+            self._gn_finish()
+            nnops.step_state_advance(self._state, self.lr, self.gamma, self.milestones, b1, b2)
+            self._adam_ranges(0, fl.n)
+            self._adam_aux()
+            self._after_update()
+            return
         # step += 1, lr after the milestones, bias corrections: computed on the device, read there by the Adam kernels
         nnops.step_state_advance(self._state, self.lr, self.gamma, self.milestones, b1, b2)
         self._adam_ranges(cut, fl.n)                  # multi-GPU: runs while the head of the buffer is still being reduced
@@ -2021,7 +2119,8 @@ class TrainEngine:
         for a in self.aux:
             if a["p"].requires_grad:
                 nnops.adam_step_dev(a["p"].data.view(-1), a["g"].view(-1), a["m"].view(-1), a["v"].view(-1), self._state,
-                                    b1, b2, self.eps, self.wd, vmax=a["vmax"].view(-1) if a["vmax"] is not None else None)
+                                    b1, b2, self.eps, self.wd, vmax=a["vmax"].view(-1) if a["vmax"] is not None else None,
+                                    guard=self._guard)
 
     def _after_update(self):
         if self.vq_kind in ("VectorQuantizer", "MultiVectorQuantizer") and self.E.requires_grad:
@@ -2146,6 +2245,8 @@ class TrainEngine:
         finally:
             self._prepared = None
         self.optimizer_step()
+        if self._guard is not None:            # copies: the guard state is rewritten by the next step
+            out.update({k: v.clone() for k, v in self._guard_out.items()})
         return out
 
     def train_step(self, input_ids, attention_mask, prepared=None, dec_ids=None, dec_mask=None, target_ids=None):

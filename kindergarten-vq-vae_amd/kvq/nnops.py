@@ -340,8 +340,15 @@ def adam_step(p32, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_d
                               float(grad_scale), stream_ptr()), "kvq_adam_step")
 
 
-def adam_step_dev(p32, g, m, v, step_state, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, vmax=None, shadow=None, grad_scale=1.0):
-    """adam_step with lr and the bias corrections read on the device from `step_state` (see step_state_advance)."""
+def adam_step_dev(p32, g, m, v, step_state, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, vmax=None, shadow=None, grad_scale=1.0,
+                  guard=None):
+    """adam_step with lr and the bias corrections read on the device from `step_state` (see step_state_advance).  guard: a gradient
+    guard state (new_grad_guard): the gradient is scaled by grad_scale * guard.coef, and nothing is stored when guard.skip is set."""
+    if guard is not None:
+        check(lib().kvq_adam_step_guarded(p32.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(vmax), _p(shadow), p32.numel(),
+                                          io_dtype_of(g), step_state.data_ptr(), float(beta1), float(beta2), float(eps),
+                                          float(weight_decay), float(grad_scale), _guard_ptr(guard), stream_ptr()), "kvq_adam_step_guarded")
+        return
     check(lib().kvq_adam_step_dev(p32.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(vmax), _p(shadow), p32.numel(),
                                   io_dtype_of(g), step_state.data_ptr(), float(beta1), float(beta2), float(eps), float(weight_decay),
                                   float(grad_scale), stream_ptr()), "kvq_adam_step_dev")
@@ -366,6 +373,54 @@ def read_step_state(step_state):
     raw = step_state.cpu()
     f = raw[1:].view(torch.float32)
     return int(raw[0]), float(f[0]), float(f[1]), float(f[2])
+
+
+# ---- gradient guard (include/kvq.h "gradient guard"): global gradient norm, clipping coefficient, non-finite step skip -----------
+def grad_sumsq_partials():
+    """Partial sums one grad_sumsq_partial call writes (a constant of the library)."""
+    return int(lib().kvq_grad_sumsq_partials())
+
+
+def new_grad_guard(device):
+    """32 zeroed bytes: struct { double sumsq; float norm, coef; uint32 skip, pad; uint64 skipped; } of include/kvq.h."""
+    return torch.zeros(4, dtype=torch.int64, device=device)
+
+
+def _guard_ptr(guard):
+    if not torch.is_tensor(guard) or guard.dtype != torch.int64 or guard.numel() != 4 or not guard.is_contiguous():
+        raise KvqError("a gradient guard state is new_grad_guard()'s tensor (4 x int64)")
+    require_gpu(guard)
+    return guard.data_ptr()
+
+
+def read_grad_guard(guard):
+    """dict(norm, coef, skip, skipped, sumsq) -- synchronises; for tests, logging and TrainEngine.skipped_steps."""
+    _guard_ptr(guard)
+    raw = guard.cpu()
+    f = raw[1:2].view(torch.float32)
+    return dict(norm=float(f[0]), coef=float(f[1]), skip=int(raw[2]) & 0xFFFFFFFF, skipped=int(raw[3]),
+                sumsq=float(raw[0:1].view(torch.float64)[0]))
+
+
+def grad_sumsq_partial(g, partials):
+    """partials (f64, grad_sumsq_partials() elements, e.g. a slice of a larger buffer) = partial sums of g**2 over the flat f32 / bf16
+    tensor g.  Deterministic; see include/kvq.h."""
+    require_gpu(g, partials)
+    if not g.is_contiguous() or g.numel() < 1:
+        raise KvqError("grad_sumsq_partial: a contiguous gradient of at least one element required")
+    if partials.dtype != torch.float64 or not partials.is_contiguous():
+        raise KvqError("grad_sumsq_partial: the partial sums are a contiguous float64 tensor")
+    check(lib().kvq_grad_sumsq_partial(g.data_ptr(), g.numel(), io_dtype_of(g), partials.data_ptr(), partials.numel(), stream_ptr()),
+          "kvq_grad_sumsq_partial")
+
+
+def grad_guard_finalize(partials, max_norm, guard):
+    """All partial sums of the step -> guard: norm, coef = min(1, max_norm / (norm + 1e-6)), or skip when the sum is not finite."""
+    require_gpu(partials)
+    if partials.dtype != torch.float64 or not partials.is_contiguous():
+        raise KvqError("grad_guard_finalize: the partial sums are a contiguous float64 tensor")
+    check(lib().kvq_grad_guard_finalize(partials.data_ptr(), partials.numel(), float(max_norm), _guard_ptr(guard), stream_ptr()),
+          "kvq_grad_guard_finalize")
 
 
 def set_seed_offset(step_state):

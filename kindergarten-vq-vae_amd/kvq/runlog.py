@@ -39,3 +39,25 @@ def init_run(project, group, job_type, config, mode, run_path):
         except ImportError:
             pass
     return JsonlRun(run_path, config)
+
+
+# ---- TrainEngine(max_grad_norm=...): the step's gradient norm and the skipped steps in the trainers' logs -------------------------
+def grad_norm_note(stats_stage_run: dict, stats_step: dict):
+    """Add the step's global gradient norm ("grad_norm_step": a device scalar of train_step's result, present only with the option
+    on) to the stage's running sum.  A skipped step's inf / NaN counts as 0.  Device arithmetic only: no synchronisation."""
+    gn = stats_step.get("grad_norm_step")
+    if gn is not None:
+        import torch
+        stats_stage_run["grad_norm_run"] = stats_stage_run.get("grad_norm_run", 0) + torch.nan_to_num(gn.float(), nan=0.0, posinf=0.0,
+                                                                                                      neginf=0.0)
+
+
+def grad_guard_epoch_record(engine, stats_stage_run: dict, n_steps: int, skipped_before: int, stage: str = "train"):
+    """End of a training stage, after its statistics were read (the one synchronisation of the epoch): ({"<stage>/grad_norm": mean
+    norm over the applied steps, "<stage>/skipped_steps": steps skipped so far} | None with the option off, steps skipped so far)."""
+    total = stats_stage_run.pop("grad_norm_run", None)
+    if engine is None or getattr(engine, "max_grad_norm", None) is None or total is None:
+        return None, skipped_before
+    skipped = int(engine.skipped_steps)
+    applied = max(n_steps - (skipped - skipped_before), 1)
+    return {f"{stage}/grad_norm": float(total) / applied, f"{stage}/skipped_steps": skipped}, skipped

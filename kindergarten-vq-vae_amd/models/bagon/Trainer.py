@@ -29,6 +29,7 @@ from torch import Tensor, no_grad, save
 
 from common.consts import *  # noqa: F401,F403
 from common.tensor_utils import replace_pct_rand_values
+from kvq.runlog import grad_guard_epoch_record, grad_norm_note
 
 
 def _tokenize(batch, tokenizer, add_special_tokens, max_length, device, side):
@@ -83,13 +84,16 @@ def step(device, model, tokenizer_encoder, tokenizer_decoder,
             if lr_sched is not None:
                 lr_sched.step()
     loss_recon_step = loss_recon_step.detach()
-    return {
+    stats = {
         "loss_recon_step": loss_recon_step,
         "loss_full_step": loss_recon_step,                                                         # Trainer.py:111
         "metric_acc_step_per_batch": acc_batch.detach(),
         "metric_acc_step_per_sentence": acc_sentence.detach(),
         "padding_tokens_pct_step": -69,
-    }, input_ids_encoder, input_ids_decoder, recon_ids, labels
+    }
+    if engine is not None and "grad_norm" in out:         # TrainEngine(max_grad_norm=...): a device scalar like the others
+        stats["grad_norm_step"] = out["grad_norm"]
+    return stats, input_ids_encoder, input_ids_decoder, recon_ids, labels
 
 
 def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batch: int):
@@ -97,6 +101,7 @@ def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batc
     stats_stage_run["loss_full_run"] += stats_step["loss_full_step"] * n_els_batch
     stats_stage_run["metric_acc_run"] += stats_step["metric_acc_step_per_batch"] * n_els_batch * 1e2
     stats_stage_run["padding_tokens_pct_run"] += stats_step["padding_tokens_pct_step"]
+    grad_norm_note(stats_stage_run, stats_step)
     return stats_stage_run
 
 
@@ -251,6 +256,7 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
         tasks = (prg.add_task(f"[bold {COLOR_TRAIN}] Train batches", total=n_batches_train),
                  prg.add_task(f"[bold {COLOR_VAL}] Val   batches", total=n_batches_val))
     hist = []
+    skipped = 0
     for epoch in range(1, n_epochs + 1):
         if prg is not None:
             prg.reset(tasks[0]); prg.reset(tasks[1])
@@ -260,6 +266,11 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
         run, n, s = _stage("train", dl_train, n_batches_train, step_kw, opt, lr_sched,
                            (encoder_perturb_train_pct, decoder_perturb_train_pct), dec, epoch, grad_sync, engine, prg, tasks and tasks[0])
         stats_train_run, stats_train_best = end_of_epoch_stats_update(run, stats_train_best, n, s)
+        guard_rec, skipped = grad_guard_epoch_record(engine, run, s, skipped)             # max_grad_norm: mean norm, skipped steps
+        if guard_rec is not None:
+            wandb_run.log({"epoch": epoch, **guard_rec})
+            if console is not None:
+                console.print(f"    | grad_norm: {guard_rec['train/grad_norm']:.6f} | skipped steps: {guard_rec['train/skipped_steps']}")
         # sentences/s of THIS rank's train stage, loop and all (end_of_epoch_stats_update has just turned the device sums into
         # floats: the stage's kernels have finished).  An extra log entry, not one of the reference's keys.
         wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": s,

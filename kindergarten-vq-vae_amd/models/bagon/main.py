@@ -91,7 +91,8 @@ def main():
         engine = TrainEngine(model, lr=LR, weight_decay=WEIGHT_DECAY, amsgrad=AMSGRAD,
                              milestones=MILESTONES if LR_SCHEDULER == "MultiStepLR" else None, gamma=GAMMA, bucket_mib=GRAD_BUCKET_MIB,
                              fp8_forward=FP8_FORWARD if FP8_FORWARD else None,       # (None: the KVQ_FP8 environment switch decides)
-                             fp8_backward=FP8_BACKWARD if FP8_BACKWARD else None)     # (None: KVQ_FP8_BACKWARD)
+                             fp8_backward=FP8_BACKWARD if FP8_BACKWARD else None,     # (None: KVQ_FP8_BACKWARD)
+                             max_grad_norm=MAX_GRAD_NORM)                             # (None: off, or KVQ_MAX_GRAD_NORM)
         if TOKEN_CACHE and same_tok:
             for c in caches:
                 c.packed_pad_id = engine.pad_idx if not any_perturb else "off"     # perturbed ids are sorted by the engine itself
@@ -105,7 +106,8 @@ def main():
     run_id = ddp.same_everywhere(datetime.now().strftime(RUN_ID_TIMESTAMP_FORMAT))     # one run directory for all ranks
     run_path = f"{RUNS_DIR}/{run_id}"
     run_conf = get_config()
-    run_conf.update({"n_params": model.model_params_summary_dict(), "optimizer": str(opt), "run_id": run_id, "world_size": world})
+    run_conf.update({"n_params": model.model_params_summary_dict(), "optimizer": str(opt), "run_id": run_id, "world_size": world,
+                     "max_grad_norm": engine.max_grad_norm if engine is not None else None})     # what the step really runs with
     if is_main:
         os.makedirs(run_path, exist_ok=True)
         with open(f"{run_path}/run_conf.json", "w") as fp:

@@ -24,6 +24,7 @@ import torch
 from torch import Tensor, no_grad, save
 
 from common.consts import *  # noqa: F401,F403  (colours / emoji)
+from kvq.runlog import grad_guard_epoch_record, grad_norm_note
 
 
 def tokenize_batch(batch, tokenizer, tokenizer_add_special_tokens: bool, max_length: int, device):
@@ -49,11 +50,14 @@ def step(device, model, tokenizer, tokenizer_add_special_tokens: bool, opt,
         # tick) itself; the loss weights were given to its constructor
         out = engine.train_step(input_ids, attention_mask, prepared=batch.get("packed") if isinstance(batch, dict) else None) \
             if opt is not None else engine.eval_step(input_ids, attention_mask)
-        return {
+        stats = {
             "loss_recon_step": out["loss_recon"].detach(), "loss_vq_step": out["loss_vq"].detach(),
             "metric_perp_step": out["perplexity"].detach(), "loss_full_step": (out["loss_recon"] + out["loss_vq"]).detach(),
             "metric_acc_step": out["acc"].detach(), "padding_tokens_pct_step": -69,
-        }, input_ids, out["recon_ids"]
+        }
+        if "grad_norm" in out:                    # TrainEngine(max_grad_norm=...): a device scalar like the others
+            stats["grad_norm_step"] = out["grad_norm"]
+        return stats, input_ids, out["recon_ids"]
 
     loss_vq_step, metric_perp_step, _indices, loss_recon_step, acc_step, recon_ids = \
         model.forward_loss(input_ids, attention_mask)
@@ -91,6 +95,7 @@ def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batc
     stats_stage_run["loss_full_run"] += stats_step["loss_full_step"] * n_els_batch
     stats_stage_run["metric_acc_run"] += stats_step["metric_acc_step"] * n_els_batch * 1e2
     stats_stage_run["padding_tokens_pct_run"] += stats_step["padding_tokens_pct_step"]
+    grad_norm_note(stats_stage_run, stats_step)
     return stats_stage_run
 
 
@@ -234,6 +239,7 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
                  prg.add_task(f"[bold {COLOR_VAL}] Val   batches", total=n_batches_val))
     stats_train_best, stats_val_best = init_stats_best(), init_stats_best()
     history = []
+    skipped = 0
     for epoch in range(1, n_epochs + 1):
         if tasks:
             prg.reset(tasks[1]); prg.reset(tasks[2])
@@ -246,6 +252,11 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
                                          opt, lr_sched, weights, vocab_size, decode_now, epoch, console, max_length, grad_sync, tick,
                                          engine=engine)
         stats_train_run, stats_train_best = end_of_epoch_stats_update(run, stats_train_best, n_els, n_steps)
+        guard_rec, skipped = grad_guard_epoch_record(engine, run, n_steps, skipped)       # max_grad_norm: mean norm, skipped steps
+        if guard_rec is not None:
+            wandb_run.log({"epoch": epoch, **guard_rec})
+            if console is not None:
+                console.print(f"    | grad_norm: {guard_rec['train/grad_norm']:.6f} | skipped steps: {guard_rec['train/skipped_steps']}")
         # sentences/s of THIS rank's train stage, loop and all (end_of_epoch_stats_update has just turned the device sums into
         # floats: the stage's kernels have finished).  An extra log entry, not one of the reference's keys.
         wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": n_steps,

@@ -35,6 +35,7 @@ COMPUTE_DTYPE = "bfloat16"           # bfloat16 | float32
 USE_ENGINE = True                    # kvq.engine.TrainEngine (explicit fwd/bwd on flat buffers) when the model shape allows
 FP8_FORWARD = False                  # extension (BASELINE.json configs[4]): forward GEMMs on the fp8 matrix cores -- False | True | "wide" | "all"
 FP8_BACKWARD = False                 # option on top of FP8_FORWARD: input-gradient GEMMs on fp8 (e5m2 gradients, transposed e4m3 weights); DESIGN.md section 5
+MAX_GRAD_NORM = None                 # None (off) | float > 0 | float("inf"): the engine step clips its gradient by the global norm and skips non-finite steps (inf: measure and skip only); KVQ_MAX_GRAD_NORM; DESIGN.md section 5b
 
 VQ_MODE = "VectorQuantizer"          # VectorQuantizer | GumbelQuantizer | MultiVectorQuantizer (extension: VQ_N_FACTORS codebooks)
 VQ_N_FACTORS = 1                     # MultiVectorQuantizer: codebooks = slices of the encoder output (must divide VQ_E_DIM)
@@ -86,6 +87,8 @@ for _k in [k for k in list(globals()) if k.isupper()]:
             globals()[_k] = _ast.literal_eval(_v)
         except (ValueError, SyntaxError):
             globals()[_k] = _v
+if isinstance(MAX_GRAD_NORM, str):       # KVQ_MAX_GRAD_NORM=inf is no python literal; empty = off (as TrainEngine reads the variable)
+    MAX_GRAD_NORM = float(MAX_GRAD_NORM) if MAX_GRAD_NORM.strip() else None
 
 
 def get_config() -> dict:

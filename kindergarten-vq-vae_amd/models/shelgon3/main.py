@@ -113,7 +113,8 @@ def main():
                              loss_recon_scale=LOSS_RECON_RESCALE_FACTOR * LOSS_RECON_WEIGHT,
                              loss_vq_scale=LOSS_VQ_RESCALE_FACTOR * LOSS_VQ_WEIGHT, bucket_mib=GRAD_BUCKET_MIB,
                              fp8_forward=FP8_FORWARD if FP8_FORWARD else None,       # (None: the KVQ_FP8 environment switch decides)
-                             fp8_backward=FP8_BACKWARD if FP8_BACKWARD else None)     # (None: KVQ_FP8_BACKWARD)
+                             fp8_backward=FP8_BACKWARD if FP8_BACKWARD else None,     # (None: KVQ_FP8_BACKWARD)
+                             max_grad_norm=MAX_GRAD_NORM)                             # (None: off, or KVQ_MAX_GRAD_NORM)
         if TOKEN_CACHE:
             for c in caches:          # the packed sort files the MODEL's padding row under -1 (not the tokenizer's pad id)
                 c.packed_pad_id = engine.pad_idx
@@ -131,7 +132,8 @@ def main():
     run_id = ddp.same_everywhere(datetime.now().strftime(RUN_ID_TIMESTAMP_FORMAT))     # one run directory for all ranks
     run_path = f"{RUNS_DIR}/{run_id}"
     run_conf = get_config()
-    run_conf.update({"n_params": model.model_params_summary_dict(), "optimizer": str(opt), "run_id": run_id, "world_size": world})
+    run_conf.update({"n_params": model.model_params_summary_dict(), "optimizer": str(opt), "run_id": run_id, "world_size": world,
+                     "max_grad_norm": engine.max_grad_norm if engine is not None else None})     # what the step really runs with
     if is_main:
         os.makedirs(run_path, exist_ok=True)
         console.print(f"Run ID: [bold {COLOR_RUN_ID}]{run_id}\n")
