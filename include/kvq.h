@@ -559,6 +559,48 @@ int kvq_adam_step_guarded_fp8(float* p, const void* g, float* m, float* v, float
                               void* w8_mirror, const int* span_segment, const float* seg_scale, const int64_t* seg_off,
                               const int64_t* seg_n, int nseg, int64_t first_element, const void* guard, void* stream);
 
+/* ---- codebook revival: a dead code restarts from an encoder output of the current batch (csrc/kvq_vq_revive.hip) -------------
+ * Extension, absent from the reference, off by default (VectorQuantizer(revive_after=T)).  State per quantiser, device memory:
+ *     idle [G, K] int32, zero-initialised: consecutive TRAINING steps in which code k of codebook g won no token
+ *     counter, 16 bytes, 8-byte aligned, zero-initialised:   struct { uint32_t last, pad; uint64_t total; }
+ * A training step runs three entry points on its own stream with no host round trip (kernels only: no memset, no memcpy, every
+ * one may be captured), with T = revive_after >= 1:
+ * kvq_vq_usage_flags     used[g, k] = 1 if some token n has idx[g, n] == k, else 0 (idx [G, N] int64, 1 <= N < 2^32).  An index
+ *                        outside [0, K) is ignored (the fused tail leaves -1 for an all-NaN row).  EVERY element of used[G, K] is
+ *                        written by the one launch: a workgroup owns 64 codes of one codebook and scans that codebook's indices;
+ *                        no clear, no atomics.
+ *                        Data parallel: the caller all-reduces `used` with MAX -- usage is a property of the global batch.
+ * kvq_vq_revive_select   idle' = used ? 0 : min(idle + 1, INT32_MAX), written back for every code.  A code is DEAD when idle' >= T;
+ *                        work on any other code ends after reading idle.  For a dead code, with c = g K + k:
+ *                            r = philox4x32(c0 = c, c1 = 0, c2 = 0x52455649, c3 = 0x5eed; key = seed)     (4 x 32 bits)
+ *                        where seed += the device step count when kvq_set_seed_offset is active (as every dropout kernel does);
+ *                        0x52455649 ("REVI") is a site no dropout site reaches, those are a small counter.
+ *                            owner rank = r.y %% world,      donor token n = ((uint64) r.x * N) >> 32
+ *                            rows[g, k, :] = (float) z[g, n, :] on the owner (exact: z is f32 or bf16), +0.0f on every other rank
+ *                        z [G, N, D] io_dtype (the layout kvq_vq_forward takes), rows [G, K, D] f32, both 16-byte aligned; rows of
+ *                        codes that are not dead are not written.  16-byte accesses where the row pitch of z allows them (D %% 4 == 0
+ *                        in f32, D %% 8 == 0 in bf16), one element at a time otherwise.
+ *                        Data parallel: the caller all-reduces `rows` with SUM -- one rank contributes the value and the others
+ *                        zeros, so the sum is exact in any order (a -0.0 becomes +0.0).
+ * kvq_vq_revive_apply    after the codebook's own update of the step (Adam or EMA), before anything derived from the codebook is
+ *                        rebuilt.  counter.last = number of dead codes (idle >= T), counter.total += last: written by every call,
+ *                        by one workgroup, before the rows move.  For every dead code: E[g, k, :] = rows[g, k, :]; the row of the
+ *                        Adam moments m, v, vmax = 0; ema_n[g, k] = 1 and ema_m[g, k, :] = rows[g, k, :] (what the constructor
+ *                        gives a fresh code); idle = 0.  m, v, vmax, ema_n, ema_m may each be NULL.  A code that is not dead is not
+ *                        touched at all.  E [G, K, D] f32 and rows 16-byte aligned; 16-byte accesses when D %% 4 == 0 and every
+ *                        optional pointer is 16-byte aligned.
+ * Deterministic: no floating-point atomics (no atomics at all), one wave per code, the same inputs give the same bits; with the
+ * same seed, idle and (reduced) used every rank takes the same decisions.  Two dead codes may draw the same token: the lower
+ * index then wins the arg-min tie, the other goes idle again and is redrawn T steps later under another step seed.  Revival is
+ * not a gradient step: the gradient guard's skip does not gate it (nor does it gate the EMA update).
+ * Every bad argument is refused before any launch: a NULL required pointer, N, K, D or G < 1, N >= 2^32, G K >= 2^31,
+ * revive_after < 1, world < 1, rank outside [0, world), an unknown dtype, a misaligned z, rows or E. */
+int kvq_vq_usage_flags(const int64_t* idx, int64_t N, int K, int G, int32_t* used, void* stream);
+int kvq_vq_revive_select(const void* z, const int32_t* used, int64_t N, int K, int D, int G, int io_dtype, int revive_after,
+                         uint64_t seed, int rank, int world, int32_t* idle, float* rows, void* stream);
+int kvq_vq_revive_apply(const float* rows, int K, int D, int G, int revive_after, int32_t* idle, float* E, float* m, float* v,
+                        float* vmax, float* ema_n, float* ema_m, void* counter, void* stream);
+
 
 /* ---- the consumer of the code indices: word x code counts ------------------------------------------------------------------
  * Replaces the per-token Python walk of analyses/unsupervised_vq_disentanglement/unsupervised_vq_disentanglement.py:166-200

@@ -135,6 +135,9 @@ SIGNATURES = {
     "kvq_adam_step_guarded": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "kvq_adam_step_guarded_fp8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp,
                                          _int, _i64, _vp, _vp]),
+    "kvq_vq_usage_flags": (_int, [_vp, _i64, _int, _int, _vp, _vp]),
+    "kvq_vq_revive_select": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, C.c_uint64, _int, _int, _vp, _vp, _vp]),
+    "kvq_vq_revive_apply": (_int, [_vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kvq_embed_grad_workspace_bytes": (_sz, [_i64, _int]),
     "kvq_embed_grad": (_int, [_vp, _vp, _vp, _i64, _int, _i64, _int, _vp, _int, _int, _vp, _sz, _vp]),
     "kvq_dropout": (_int, [_vp, _i64, _f32, C.c_uint64, C.c_uint32, _int, _vp, _vp]),

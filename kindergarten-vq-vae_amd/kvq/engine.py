@@ -35,7 +35,7 @@ import torch.nn.functional as F
 
 from . import nnops
 from ._ffi import FP8_E5M2, KvqError, check, io_dtype_of, lib, stream_ptr
-from .functional import _workspace
+from .functional import _workspace, check_revive_after, new_revive_counter, read_revive_counter, vq_revive_apply, vq_revive_select
 
 V_ALIGN = 64   # vocabulary rows of the LM head are padded so logits rows are 128-byte aligned
 
@@ -307,6 +307,8 @@ class _StepGraphs:
                     self.graphs[-1].capture_end()
                     if eng._guard is not None:      # grad_norm / grad_clip_coef: views of the guard state, run() hands out copies
                         self.out.update(eng._guard_out)
+                    if eng.revive_after is not None:
+                        self.out["codes_revived"] = eng._rv_counter[0]
                     ok = True
                 finally:
                     eng._cap = None
@@ -388,6 +390,11 @@ class TrainEngine:
                  bucket_mib=64, process_group=None, fp8_forward=None, fp8_backward=None, max_grad_norm=None):
         self.model = model
         self.max_grad_norm = self.check_max_grad_norm(max_grad_norm, env=True)     # (before anything is laid out: a bad value changes nothing)
+        # option, off by default: codebook revival.  The quantiser's revive_after; None there: KVQ_VQ_REVIVE_AFTER
+        # from the environment, as max_grad_norm reads KVQ_MAX_GRAD_NORM (unset / empty: off).  A model without a quantiser ignores it.
+        self.revive_after = None
+        if hasattr(model, "vector_quantizer"):
+            self.revive_after = check_revive_after(getattr(model.vector_quantizer, "revive_after", None), env=True)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise KvqError("TrainEngine needs the model on an MI355X (there is no CPU path)")
@@ -548,6 +555,9 @@ class TrainEngine:
                 if self.Dg % 32 == 0 else None
             self._E_version = None
         elif self.vq_kind == "GumbelQuantizer":
+            if self.revive_after is not None:
+                raise KvqError("TrainEngine: codebook revival (revive_after / KVQ_VQ_REVIVE_AFTER) is defined for the arg-min "
+                               "quantisers, not for GumbelQuantizer")
             gq = model.vector_quantizer
             if gq.n_embed > 1024:
                 raise KvqError("TrainEngine: the Gumbel row kernel holds at most 1024 codes")
@@ -609,6 +619,19 @@ class TrainEngine:
             if self.dtype != torch.bfloat16:
                 raise KvqError("TrainEngine: fp8 forward GEMMs need the bf16 compute dtype")
             self._fp8_setup()
+        # Off = no idle buffer, no launch added, today's graphs.  On: usage flags + select behind the quantiser's forward launch (the
+        # eager interlude of the step), apply behind the codebook's own update (_revive_apply); state on the module when it has some
+        self._rv_pending = self._in_fb = False
+        self.revive_keep_donors = False          # tests: keep a copy of the z the select kernel read (revive_donors)
+        if self.revive_after is not None:
+            vq = model.vector_quantizer
+            own = getattr(vq, "revive_after", None) is None           # the option came from the environment: the state is the engine's
+            self._rv_idle = torch.zeros((self.G, self.K), dtype=torch.int32, device=dev) if own else vq.code_idle
+            self._rv_counter = new_revive_counter(dev) if own else vq.revive_counter
+            if self._rv_idle.numel() != self.G * self.K or not self._rv_idle.is_cuda:
+                raise KvqError(f"TrainEngine: code_idle {tuple(self._rv_idle.shape)} does not match {self.G} x {self.K} codes on the device")
+            self._rv_used = torch.zeros((self.G, self.K), dtype=torch.int32, device=dev)
+            self._rv_rows = torch.zeros((self.G, self.K, self.Dg), dtype=torch.float32, device=dev)
         model.__dict__["_kvq_engine"] = self
         self._param_versions = self._versions()
         # gradient all-reduce chunks (tail first)
@@ -1386,6 +1409,7 @@ class TrainEngine:
         pre = getattr(self, "_prepared", None) or {}            # this batch's (sorted ids, order) per side: _normalise_prepared()
         self._sorted = {"enc.emb.": pre.get("enc"), "dec.emb.": pre.get("dec") if dec_ids is not None else "enc.emb."}
         nnops.set_seed_offset(self._state)        # dropout seeds of this engine's launches = _step_seed + device step count
+        self._in_fb = True
         try:
             self._q_training = training if quantizer_training is None else bool(quantizer_training)
             with torch.no_grad():            # the schedule IS the backward pass: no autograd graph over the few torch ops in it
@@ -1411,6 +1435,7 @@ class TrainEngine:
                 return out
         finally:
             self._bwd8_mode = None
+            self._in_fb = False
             nnops.set_seed_offset(None)
 
     def forward_logits(self, enc_ids, enc_mask, dec_ids=None, dec_mask=None, training=False, quantizer_training=None):
@@ -1712,7 +1737,8 @@ class TrainEngine:
                 z_q = torch.empty_like(z)
                 idx = torch.empty(N * self.G, dtype=torch.int64, device=self.dev)
                 vq_out = torch.empty(2, dtype=torch.float32, device=self.dev)
-            self._eager(lambda: self._vq_forward(z, z_q, idx, vq_out))
+            revive = compute_grads and self.revive_after is not None        # training steps only
+            self._eager(lambda: self._vq_forward(z, z_q, idx, vq_out, revive))
             loss_vq, perplexity = vq_out[0], vq_out[1]
             enc_out = z_q
             indices = idx.view(self.G, N).t().reshape(B, S, self.G)          # [B, S, 1] for the reference's single codebook
@@ -1901,7 +1927,7 @@ class TrainEngine:
                                           self.beta_vq, z_q.data_ptr(), idx.data_ptr(), loss.data_ptr(), perp.data_ptr(), None,
                                           ws.data_ptr(), ws.numel(), stream_ptr()), "kvq_vq_forward_packed")
 
-    def _vq_forward(self, z, z_q, idx, vq_out):
+    def _vq_forward(self, z, z_q, idx, vq_out, revive=False):
         """kvq_vq_forward on the encoder output: one codebook (the reference's VectorQuantizer), or G codebooks on G column
         slices as one grouped launch (MultiVectorQuantizer: loss / perplexity = mean over the factors)."""
         N, H = z.shape
@@ -1925,6 +1951,57 @@ class TrainEngine:
             self._buf("ema_z", zsrc.shape, zsrc.dtype).copy_(zsrc)
             self._buf("ema_idx", idx.shape, idx.dtype).copy_(idx)
             self._ema_shapes = (tuple(zsrc.shape), zsrc.dtype, tuple(idx.shape))
+        if revive:
+            self._revive_select(zsrc, idx)
+
+    def _revive_select(self, zsrc, idx):
+        """Codebook revival, first half, in the quantiser's interlude where z and idx are live: usage flags, idle counters and
+        the donor rows of the codes that are now dead (kvq.functional.vq_revive_select; data parallel: its two small all-reduces
+        sit in the hand-over between the step's graphs).  The kernel's seed is _step_seed + the device step count BEFORE this
+        step's kvq_step_state_advance -- the seed of this step's dropout masks.  A replayed interlude runs outside
+        forward_backward(): it sets the seed offset itself."""
+        self._rv_pending = True
+        if self._cap is not None:          # capture runs an interlude once on the unwritten buffers of graphs that have not run:
+            return                         # that is no training step -- idle does not advance; the replays (no _cap) do the work
+        if self.revive_keep_donors:
+            self._buf("revive_z", (self.G, zsrc.shape[-2], self.Dg), zsrc.dtype).copy_(zsrc.view(self.G, -1, self.Dg))
+            self._rv_donor_shape = ((self.G, zsrc.shape[-2], self.Dg), zsrc.dtype)
+        nnops.set_seed_offset(self._state)
+        try:
+            vq_revive_select(zsrc, idx, self._rv_idle, self.E.data, self.revive_after, self._step_seed, used=self._rv_used,
+                             rows=self._rv_rows, group=self.group)
+        finally:
+            if not self._in_fb:
+                nnops.set_seed_offset(None)
+
+    def _revive_apply(self):
+        """Second half, behind the codebook's own update (Adam on the aux parameters, or the EMA step) and before the codebook is
+        repacked: the dead codes take their rows, their moments restart.  Not gated by the gradient guard's skip."""
+        if not self._rv_pending:
+            return
+        self._rv_pending = False
+        vq = self.model.vector_quantizer
+        a = next((x for x in self.aux if x["p"] is self.E), None) if self.E.requires_grad else None
+        vq_revive_apply(self._rv_rows, self._rv_idle, self.E.data, self.revive_after, self._rv_counter,
+                        m=a["m"] if a else None, v=a["v"] if a else None, vmax=a["vmax"] if a else None,
+                        ema_n=vq.ema_n if self.vq_ema else None, ema_m=vq.ema_m if self.vq_ema else None)
+
+    @property
+    def code_idle(self):
+        """[G, K] int32 view of the idle counters (revive_after only; None otherwise): training steps since code k of codebook g
+        last won a token."""
+        return self._rv_idle.view(self.G, self.K) if self.revive_after is not None else None
+
+    @property
+    def revived_codes(self):
+        """Codes revived so far (revive_after only; synchronises)."""
+        return read_revive_counter(self._rv_counter)["total"] if self.revive_after is not None else 0
+
+    @property
+    def revive_donors(self):
+        """[G, N, D] copy of the encoder outputs the last select kernel drew its donors from (revive_keep_donors = True only)."""
+        shape, dt = self._rv_donor_shape
+        return self._buf("revive_z", shape, dt)
 
     def _vq_backward(self, z, idx, g_enc):
         N, H = z.shape
@@ -2103,6 +2180,7 @@ class TrainEngine:
             nnops.step_state_advance(self._state, self.lr, self.gamma, self.milestones, b1, b2)
             self._adam_ranges(0, fl.n)
             self._adam_aux()
+            self._revive_apply()
             self._after_update()
             return
         # step += 1, lr after the milestones, bias corrections: computed on the device, read there by the Adam kernels
@@ -2112,6 +2190,7 @@ class TrainEngine:
             self._eager(self._exchange_tail)
             self._adam_ranges(0, cut)
         self._adam_aux()
+        self._revive_apply()
         self._after_update()
 
     def _adam_aux(self):
@@ -2123,7 +2202,7 @@ class TrainEngine:
                                     guard=self._guard)
 
     def _after_update(self):
-        if self.vq_kind in ("VectorQuantizer", "MultiVectorQuantizer") and self.E.requires_grad:
+        if self.vq_kind in ("VectorQuantizer", "MultiVectorQuantizer") and (self.E.requires_grad or self.revive_after is not None):
             self._repack_codebook()
         if self.fp8:
             self._fp8_quantize_weights(in_step=True)
@@ -2247,6 +2326,8 @@ class TrainEngine:
         self.optimizer_step()
         if self._guard is not None:            # copies: the guard state is rewritten by the next step
             out.update({k: v.clone() for k, v in self._guard_out.items()})
+        if self.revive_after is not None:      # counter.last (its upper word is padding: 0), rewritten by the next step
+            out["codes_revived"] = self._rv_counter[0].clone()
         return out
 
     def train_step(self, input_ids, attention_mask, prepared=None, dec_ids=None, dec_mask=None, target_ids=None):

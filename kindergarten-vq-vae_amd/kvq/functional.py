@@ -145,6 +145,124 @@ def vq_ema_update(z, idx, ema_n, ema_m, E, decay: float, eps: float = 1e-5):
                               ws.data_ptr(), ws.numel(), stream_ptr()), "kvq_vq_ema_update")
 
 
+REVIVE_SITE = 0x52455649          # the Philox site of the donor draw (include/kvq.h "codebook revival")
+
+
+def check_revive_after(v, env=False):
+    """None (off) or the int >= 1 a quantiser / TrainEngine accepts as revive_after; anything else raises KvqError.
+    env: None means KVQ_VQ_REVIVE_AFTER from the environment (unset or empty: off)."""
+    import os
+    if v is None and env and os.environ.get("KVQ_VQ_REVIVE_AFTER", "") != "":
+        text = os.environ["KVQ_VQ_REVIVE_AFTER"]
+        try:
+            v = int(text)
+        except ValueError:
+            raise _ffi.KvqError(f"KVQ_VQ_REVIVE_AFTER (revive_after) must be an integer >= 1, got {text!r}") from None
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > 0x7FFFFFFF:
+        raise _ffi.KvqError(f"revive_after must be None or an integer >= 1, got {v!r}")
+    return v
+
+
+def new_revive_counter(device=None) -> torch.Tensor:
+    """The 16-byte revival counter struct { uint32_t last, pad; uint64_t total; } as two int64 words, zeroed."""
+    return torch.zeros(2, dtype=torch.int64, device=device)
+
+
+def read_revive_counter(counter) -> dict:
+    """dict(last, total) of a revival counter.  Synchronises."""
+    if not torch.is_tensor(counter) or counter.dtype != torch.int64 or counter.numel() != 2:
+        raise _ffi.KvqError("read_revive_counter: a revival counter is an int64 tensor of 2 words")
+    w = counter.tolist()
+    return dict(last=w[0] & 0xFFFFFFFF, total=w[1])
+
+
+def _revive_dims(z, idx, idle, E):
+    require_gpu(z, idx, idle, E)
+    G = z.shape[0] if z.dim() == 3 else 1
+    N, D = z.shape[-2], z.shape[-1]
+    K = E.numel() // (G * D)
+    if z.dim() not in (2, 3) or not z.is_contiguous() or not idx.is_contiguous() or idx.dtype != torch.int64 or idx.numel() != G * N:
+        raise _ffi.KvqError(f"vq_revive: need contiguous z[N,D] / z[G,N,D] and int64 idx[N] / idx[G,N]; got {tuple(z.shape)}, {tuple(idx.shape)}")
+    if E.dtype != torch.float32 or not E.is_contiguous() or E.numel() != G * K * D or K < 1:
+        raise _ffi.KvqError(f"vq_revive: the codebook must be contiguous float32 [G*K, D]; got {tuple(E.shape)} {E.dtype} for D={D}, G={G}")
+    if idle.dtype != torch.int32 or not idle.is_contiguous() or idle.numel() != G * K:
+        raise _ffi.KvqError(f"vq_revive: idle must be contiguous int32 [G, K] = {G} x {K}; got {tuple(idle.shape)} {idle.dtype}")
+    return G, N, K, D
+
+
+def _revive_group(group):
+    """(rank, world) of the ranks that share the revival decisions: an initialised process group with more than one rank, else (0, 1)."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        return dist.get_rank(group), dist.get_world_size(group)
+    return 0, 1
+
+
+def vq_revive_select(z, idx, idle, E, revive_after, seed, used=None, rows=None, group=None):
+    """Steps 1 - 5 of the codebook revival (include/kvq.h): usage flags of this batch (all-reduced with MAX over the ranks), the
+    idle counters, and for every code that is now dead the donor token's row in `rows` [G, K, D] f32 (all-reduced with SUM: the
+    owner rank wrote the row, the others zeros).  Returns rows.  used / rows: scratch to reuse (allocated when None).  The seed the
+    kernel sees is `seed` plus the device step count while kvq_set_seed_offset is active on the calling thread."""
+    import torch.distributed as dist
+    G, N, K, D = _revive_dims(z, idx, idle, E)
+    T = check_revive_after(revive_after)
+    if T is None:
+        raise _ffi.KvqError("vq_revive: revive_after must be an integer >= 1")
+    rank, world = _revive_group(group)
+    if used is None:
+        used = torch.empty((G, K), dtype=torch.int32, device=z.device)
+    if rows is None:
+        rows = torch.zeros((G, K, D), dtype=torch.float32, device=z.device)
+    elif world > 1:
+        rows.zero_()                  # rows of codes that are not dead are not written: keep what the ranks sum up finite
+    if used.dtype != torch.int32 or used.numel() != G * K or rows.dtype != torch.float32 or rows.numel() != G * K * D:
+        raise _ffi.KvqError("vq_revive: used must be int32 [G, K] and rows float32 [G, K, D]")
+    l = lib()
+    check(l.kvq_vq_usage_flags(idx.data_ptr(), N, K, G, used.data_ptr(), stream_ptr()), "kvq_vq_usage_flags")
+    if world > 1:
+        dist.all_reduce(used, op=dist.ReduceOp.MAX, group=group)
+    check(l.kvq_vq_revive_select(z.data_ptr(), used.data_ptr(), N, K, D, G, io_dtype_of(z), T, int(seed) & 0xFFFFFFFFFFFFFFFF, rank, world,
+                                 idle.data_ptr(), rows.data_ptr(), stream_ptr()), "kvq_vq_revive_select")
+    if world > 1:
+        dist.all_reduce(rows, op=dist.ReduceOp.SUM, group=group)
+    return rows
+
+
+def vq_revive_apply(rows, idle, E, revive_after, counter, m=None, v=None, vmax=None, ema_n=None, ema_m=None):
+    """Step 6: every dead code (idle >= revive_after) takes its row of `rows`; its Adam moments go to zero, its EMA statistics to
+    (1, row), its idle counter to 0; counter.last / .total count the codes.  Run it after the codebook's own update of the step."""
+    require_gpu(rows, idle, E, counter, m, v, vmax, ema_n, ema_m)
+    T = check_revive_after(revive_after)
+    if T is None:
+        raise _ffi.KvqError("vq_revive: revive_after must be an integer >= 1")
+    if rows.dim() != 3 or rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise _ffi.KvqError(f"vq_revive: rows must be contiguous float32 [G, K, D], got {tuple(rows.shape)} {rows.dtype}")
+    G, K, D = rows.shape
+    if E.dtype != torch.float32 or not E.is_contiguous() or E.numel() != rows.numel() or idle.dtype != torch.int32 \
+            or not idle.is_contiguous() or idle.numel() != G * K:
+        raise _ffi.KvqError("vq_revive: E must be contiguous float32 [G*K, D] and idle contiguous int32 [G, K]")
+    if counter.dtype != torch.int64 or counter.numel() != 2:
+        raise _ffi.KvqError("vq_revive: counter must be new_revive_counter()'s tensor")
+    for name, t, n in (("m", m, E.numel()), ("v", v, E.numel()), ("vmax", vmax, E.numel()), ("ema_n", ema_n, G * K), ("ema_m", ema_m, E.numel())):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
+            raise _ffi.KvqError(f"vq_revive: {name} must be contiguous float32 with {n} elements")
+    check(lib().kvq_vq_revive_apply(rows.data_ptr(), K, D, G, T, idle.data_ptr(), E.data_ptr(), _ptr(m), _ptr(v), _ptr(vmax),
+                                    _ptr(ema_n), _ptr(ema_m), counter.data_ptr(), stream_ptr()), "kvq_vq_revive_apply")
+
+
+def vq_revive(z, idx, idle, E, revive_after, seed, counter, m=None, v=None, vmax=None, ema_n=None, ema_m=None, group=None):
+    """Codebook revival (extension, off by default; include/kvq.h): a code of E that won no token of idx for revive_after
+    consecutive calls restarts from a random row of z.  z [N,D] or [G,N,D] (f32 / bf16), idx [N] or [G,N] int64, idle int32
+    [G,K], E float32 [G*K, D], counter = new_revive_counter().  In place, on the current stream, nothing read back; with an
+    initialised process group of more than one rank the decisions are those of the global batch and agree bit for bit over the
+    ranks.  = vq_revive_select + vq_revive_apply; a training step runs its codebook update (Adam or EMA) between the two."""
+    with torch.no_grad():
+        rows = vq_revive_select(z, idx, idle, E, revive_after, seed, group=group)
+        vq_revive_apply(rows, idle, E, revive_after, counter, m=m, v=v, vmax=vmax, ema_n=ema_n, ema_m=ema_m)
+
+
 def kmeans_update(z: torch.Tensor, idx: torch.Tensor, E: torch.Tensor):
     """In place: E[k] <- mean of z[idx == k] (clusters without points keep their centroid).  Returns the cluster sizes [K] int64."""
     require_gpu(z, idx, E)

@@ -61,3 +61,21 @@ def grad_guard_epoch_record(engine, stats_stage_run: dict, n_steps: int, skipped
     skipped = int(engine.skipped_steps)
     applied = max(n_steps - (skipped - skipped_before), 1)
     return {f"{stage}/grad_norm": float(total) / applied, f"{stage}/skipped_steps": skipped}, skipped
+
+
+# ---- revive_after (codebook revival): the codes a training stage restarted, in the trainers' logs ----------------------------------
+def codes_revived_note(stats_stage_run: dict, stats_step: dict):
+    """Add the step's revived-code count ("codes_revived_step": a device scalar of train_step's result, present only with the option
+    on) to the stage's running sum.  Device arithmetic only: no synchronisation."""
+    n = stats_step.get("codes_revived_step")
+    if n is not None:
+        stats_stage_run["codes_revived_run"] = stats_stage_run.get("codes_revived_run", 0) + n
+
+
+def revive_epoch_record(engine, stats_stage_run: dict, stage: str = "train"):
+    """End of a training stage, after its statistics were read: {"<stage>/codes_revived": codes restarted in this stage,
+    "<stage>/codes_revived_total": so far in the run} | None with the option off."""
+    total = stats_stage_run.pop("codes_revived_run", None)
+    if engine is None or getattr(engine, "revive_after", None) is None or total is None:
+        return None
+    return {f"{stage}/codes_revived": int(total), f"{stage}/codes_revived_total": int(engine.revived_codes)}

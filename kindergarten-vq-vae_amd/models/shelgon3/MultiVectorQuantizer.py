@@ -17,11 +17,11 @@ import torch
 import torch.nn as nn
 
 from kvq.functional import vector_quantize
-from models.shelgon3.VectorQuantizer import ema_codebook_update
+from models.shelgon3.VectorQuantizer import ema_codebook_update, register_revival, revive_codes
 
 
 class MultiVectorQuantizer(nn.Module):
-    def __init__(self, n_factors, n_e, e_dim, beta, ema_decay: float = None, ema_eps: float = 1e-5):
+    def __init__(self, n_factors, n_e, e_dim, beta, ema_decay: float = None, ema_eps: float = 1e-5, revive_after: int = None):
         super().__init__()
         if not 1 <= n_factors <= e_dim:
             raise ValueError(f"n_factors={n_factors} must be between 1 and e_dim={e_dim}")
@@ -49,6 +49,7 @@ class MultiVectorQuantizer(nn.Module):
             self.embedding.weight.requires_grad_(False)
             self.register_buffer("ema_n", torch.ones(n_factors, n_e))
             self.register_buffer("ema_m", self.embedding.weight.data.clone().view(n_factors, n_e, self.d_factor))
+        register_revival(self, revive_after, (n_factors, n_e))         # extension, off by default: see VectorQuantizer
         self.last_code_counts = None
 
     def codebooks(self):
@@ -84,3 +85,11 @@ class MultiVectorQuantizer(nn.Module):
     def ema_update(self, zg, idx):
         ema_codebook_update(zg, idx, self.ema_n, self.ema_m, self.codebooks().data, float(self.ema_decay), float(self.ema_eps))
         self.codebook_epoch = getattr(self, "codebook_epoch", 0) + 1          # see VectorQuantizer.ema_update
+
+    def revive(self, zg, idx, seed: int = 0):
+        """Codebook revival on the module path: VectorQuantizer.revive for the G codebooks at once.  zg [G, N, d_factor] (split()
+        of the step's encoder outputs, detached) and idx [G, N], or the indices [B, S, G] forward() returned.  Call it after
+        optimizer.step(); forward() does not revive on its own and an outside optimiser's moments are not reset."""
+        if idx.dim() == 3:
+            idx = idx.reshape(-1, self.n_factors).t()
+        return revive_codes(self, zg.detach().contiguous(), idx.contiguous(), self.embedding.weight.data, seed)

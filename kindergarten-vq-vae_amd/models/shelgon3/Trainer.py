@@ -24,7 +24,7 @@ import torch
 from torch import Tensor, no_grad, save
 
 from common.consts import *  # noqa: F401,F403  (colours / emoji)
-from kvq.runlog import grad_guard_epoch_record, grad_norm_note
+from kvq.runlog import codes_revived_note, grad_guard_epoch_record, grad_norm_note, revive_epoch_record
 
 
 def tokenize_batch(batch, tokenizer, tokenizer_add_special_tokens: bool, max_length: int, device):
@@ -57,6 +57,8 @@ def step(device, model, tokenizer, tokenizer_add_special_tokens: bool, opt,
         }
         if "grad_norm" in out:                    # TrainEngine(max_grad_norm=...): a device scalar like the others
             stats["grad_norm_step"] = out["grad_norm"]
+        if "codes_revived" in out:                # revive_after: codes restarted by this step, a device scalar like the others
+            stats["codes_revived_step"] = out["codes_revived"]
         return stats, input_ids, out["recon_ids"]
 
     loss_vq_step, metric_perp_step, _indices, loss_recon_step, acc_step, recon_ids = \
@@ -96,6 +98,7 @@ def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batc
     stats_stage_run["metric_acc_run"] += stats_step["metric_acc_step"] * n_els_batch * 1e2
     stats_stage_run["padding_tokens_pct_run"] += stats_step["padding_tokens_pct_step"]
     grad_norm_note(stats_stage_run, stats_step)
+    codes_revived_note(stats_stage_run, stats_step)
     return stats_stage_run
 
 
@@ -257,6 +260,11 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
             wandb_run.log({"epoch": epoch, **guard_rec})
             if console is not None:
                 console.print(f"    | grad_norm: {guard_rec['train/grad_norm']:.6f} | skipped steps: {guard_rec['train/skipped_steps']}")
+        revive_rec = revive_epoch_record(engine, run)                                     # revive_after: codes restarted this epoch / so far
+        if revive_rec is not None:
+            wandb_run.log({"epoch": epoch, **revive_rec})
+            if console is not None:
+                console.print(f"    | codes revived: {revive_rec['train/codes_revived']} | so far: {revive_rec['train/codes_revived_total']}")
         # sentences/s of THIS rank's train stage, loop and all (end_of_epoch_stats_update has just turned the device sums into
         # floats: the stage's kernels have finished).  An extra log entry, not one of the reference's keys.
         wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": n_steps,

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-from kvq.functional import vector_quantize, vq_ema_update, vq_one_hot
+from kvq.functional import (check_revive_after, new_revive_counter, vector_quantize, vq_ema_update, vq_one_hot, vq_revive)
 
 
 def ema_codebook_update(z, idx, ema_n, ema_m, E, decay, eps):
@@ -32,6 +32,28 @@ def ema_codebook_update(z, idx, ema_n, ema_m, E, decay, eps):
             E.copy_(ema_m / n.unsqueeze(-1))
 
 
+def register_revival(module, revive_after, shape):
+    """Extension (not in the reference, off unless asked for): a code that won no token for `revive_after` training steps restarts
+    from a random encoder output of the current batch (include/kvq.h "codebook revival").  Only when the option is set does the
+    module carry state for it: `code_idle` (int32, consecutive steps without a token per code; checkpointed with the model) and
+    the 16-byte counter of revived codes (a statistic of the run, not checkpointed)."""
+    module.revive_after = check_revive_after(revive_after)
+    if module.revive_after is not None:
+        module.register_buffer("code_idle", torch.zeros(shape, dtype=torch.int32))
+        module.register_buffer("revive_counter", new_revive_counter(), persistent=False)
+
+
+def revive_codes(module, z, idx, E, seed):
+    """What VectorQuantizer.revive / MultiVectorQuantizer.revive share: kvq.functional.vq_revive on the module's state."""
+    if module.revive_after is None:
+        raise RuntimeError(f"{type(module).__name__}.revive: the module was built without revive_after")
+    vq_revive(z, idx.contiguous(), module.code_idle, E, module.revive_after, seed, module.revive_counter,
+              ema_n=getattr(module, "ema_n", None) if module.ema_decay is not None else None,
+              ema_m=getattr(module, "ema_m", None) if module.ema_decay is not None else None)
+    module.codebook_epoch = getattr(module, "codebook_epoch", 0) + 1         # a raw-pointer write of the codebook, as ema_update's
+    return module.revive_counter[0].clone()                                   # counter.last (pad is 0): codes revived by this call
+
+
 class VectorQuantizer(nn.Module):
     """Discretization bottleneck of the VQ-VAE.
 
@@ -39,7 +61,8 @@ class VectorQuantizer(nn.Module):
     reference's loss (VectorQuantizer.py:76-77: `mean((sg[z_q]-z)^2) + beta*mean((z_q-sg[z])^2)`).
     """
 
-    def __init__(self, n_e, e_dim, beta, vq_codebook_init_values: Tensor = None, ema_decay: float = None, ema_eps: float = 1e-5):
+    def __init__(self, n_e, e_dim, beta, vq_codebook_init_values: Tensor = None, ema_decay: float = None, ema_eps: float = 1e-5,
+                 revive_after: int = None):
         super().__init__()
         self.n_e = n_e
         self.e_dim = e_dim
@@ -56,6 +79,7 @@ class VectorQuantizer(nn.Module):
             self.embedding.weight.requires_grad_(False)
             self.register_buffer("ema_n", torch.ones(n_e))
             self.register_buffer("ema_m", self.embedding.weight.data.clone())
+        register_revival(self, revive_after, (n_e,))
         # The reference always builds min_encodings [N,K]; its only caller drops it (Shelgon.py:58).  Keep the
         # contract by default, let the training path switch the 4*N*K-byte write off.
         self.materialize_min_encodings = True
@@ -91,3 +115,14 @@ class VectorQuantizer(nn.Module):
         # the kernel writes the codebook through a raw pointer (no tensor-version bump): tell whoever caches a derived copy
         # (the TrainEngine's fragment-ordered pack) that it is stale
         self.codebook_epoch = getattr(self, "codebook_epoch", 0) + 1
+
+    def revive(self, z2d, idx, seed: int = 0):
+        """Codebook revival for users of the module under torch autograd (revive_after set; the TrainEngine runs its own, inside
+        the step): call it AFTER optimizer.step() with the step's encoder outputs z2d [N, e_dim] (detached) and codes idx [N].
+        Counts the step in `code_idle` and restarts every code that has now gone revive_after steps without a token from a random
+        row of z2d (drawn from `seed`: pass another one every step, e.g. a base seed plus the step count).  Returns the number of
+        codes revived as a device tensor; nothing is read back.
+        forward() does not revive on its own: writing the codebook through a raw pointer between forward and backward would
+        corrupt the operand autograd saved.  The moments an outside optimiser keeps for a revived row are NOT reset (the engine
+        resets its own); with ema_decay the row's EMA statistics restart as the constructor sets them."""
+        return revive_codes(self, z2d.detach().view(-1, self.e_dim), idx.reshape(-1), self.embedding.weight.data, seed)

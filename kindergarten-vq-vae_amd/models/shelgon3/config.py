@@ -40,6 +40,7 @@ MAX_GRAD_NORM = None                 # None (off) | float > 0 | float("inf"): th
 VQ_MODE = "VectorQuantizer"          # VectorQuantizer | GumbelQuantizer | MultiVectorQuantizer (extension: VQ_N_FACTORS codebooks)
 VQ_N_FACTORS = 1                     # MultiVectorQuantizer: codebooks = slices of the encoder output (must divide VQ_E_DIM)
 VQ_EMA_DECAY = None                  # extension, default off: EMA codebook update instead of the codebook gradient (e.g. 0.99)
+VQ_REVIVE_AFTER = None               # extension, default off: None | int >= 1 -- a code that won no token for this many training steps restarts from a random encoder output of the batch; KVQ_VQ_REVIVE_AFTER; DESIGN.md section 5c
 VQ_N_E = 512
 VQ_E_DIM = 768
 VQ_BETA = 0.25
@@ -89,6 +90,10 @@ for _k in [k for k in list(globals()) if k.isupper()]:
             globals()[_k] = _v
 if isinstance(MAX_GRAD_NORM, str):       # KVQ_MAX_GRAD_NORM=inf is no python literal; empty = off (as TrainEngine reads the variable)
     MAX_GRAD_NORM = float(MAX_GRAD_NORM) if MAX_GRAD_NORM.strip() else None
+if isinstance(VQ_REVIVE_AFTER, str) and not VQ_REVIVE_AFTER.strip():      # KVQ_VQ_REVIVE_AFTER= (empty) = off, as TrainEngine reads the variable
+    VQ_REVIVE_AFTER = None
+if VQ_REVIVE_AFTER is not None and (isinstance(VQ_REVIVE_AFTER, bool) or not isinstance(VQ_REVIVE_AFTER, int) or VQ_REVIVE_AFTER < 1):
+    raise ValueError(f"VQ_REVIVE_AFTER (KVQ_VQ_REVIVE_AFTER) must be None or an integer >= 1, got {VQ_REVIVE_AFTER!r}")
 
 
 def get_config() -> dict:

@@ -72,11 +72,11 @@ def main():
     if VQ_MODE == "VectorQuantizer":
         init = torch.load(VQ_CODEBOOK_INIT_VALUES_PATH)["codebook_init_values"] if VQ_CODEBOOK_INIT_VALUES_PATH else None
         vector_quantizer = VectorQuantizer(n_e=VQ_N_E, e_dim=VQ_E_DIM, beta=VQ_BETA, vq_codebook_init_values=init,
-                                           ema_decay=VQ_EMA_DECAY)
+                                           ema_decay=VQ_EMA_DECAY, revive_after=VQ_REVIVE_AFTER)
         vector_quantizer.materialize_min_encodings = False          # the model drops min_encodings (Shelgon.py:58)
     elif VQ_MODE == "MultiVectorQuantizer":                         # extension (BASELINE.json configs[4]), off by default
         vector_quantizer = MultiVectorQuantizer(n_factors=VQ_N_FACTORS, n_e=VQ_N_E, e_dim=VQ_E_DIM, beta=VQ_BETA,
-                                                ema_decay=VQ_EMA_DECAY)
+                                                ema_decay=VQ_EMA_DECAY, revive_after=VQ_REVIVE_AFTER)
     elif VQ_MODE == "GumbelQuantizer":                              # main.py:68-73
         vector_quantizer = GumbelQuantizer(enc_out_size=ENC_OUT_SIZE, n_embed=VQ_N_E, embedding_dim=VQ_E_DIM,
                                            temperature=VQ_TEMPERATURE, kl_div_scale=VQ_KL_DIV_SCALE,
@@ -133,7 +133,8 @@ def main():
     run_path = f"{RUNS_DIR}/{run_id}"
     run_conf = get_config()
     run_conf.update({"n_params": model.model_params_summary_dict(), "optimizer": str(opt), "run_id": run_id, "world_size": world,
-                     "max_grad_norm": engine.max_grad_norm if engine is not None else None})     # what the step really runs with
+                     "max_grad_norm": engine.max_grad_norm if engine is not None else None,      # what the step really runs with
+                     "vq_revive_after": engine.revive_after if engine is not None else getattr(vector_quantizer, "revive_after", None)})
     if is_main:
         os.makedirs(run_path, exist_ok=True)
         console.print(f"Run ID: [bold {COLOR_RUN_ID}]{run_id}\n")
