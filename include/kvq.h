@@ -559,6 +559,30 @@ int kvq_adam_step_guarded_fp8(float* p, const void* g, float* m, float* v, float
                               void* w8_mirror, const int* span_segment, const float* seg_scale, const int64_t* seg_off,
                               const int64_t* seg_n, int nseg, int64_t first_element, const void* guard, void* stream);
 
+/* ---- gradient accumulation over the micro-batches of one optimiser step (csrc/kvq_accum.hip) ----------------------------------
+ * Extension, off by default (TrainEngine(grad_accum=A)): forward and backward run A times, Adam once, on the MEAN of the A
+ * gradients -- (loss / A).backward() A times, then opt.step().  The flat gradient is bf16 and rewritten by every backward, so the sum
+ * is kept in an f32 accumulator of the same length.
+ * accumulation state: 16 bytes of device memory, 8-byte aligned, zero-initialised:
+ *     struct { uint64_t tick; uint32_t micro, pad; }
+ * tick counts finished micro-steps and is never reset; micro = tick mod A is the position inside the current cycle.  tick is the
+ * FIRST word on purpose: kvq_set_seed_offset takes a pointer to a uint64, and an accumulating step points the dropout seeds at this
+ * state instead of the step state -- the optimiser step count does not move between the micro-steps of one cycle, which would
+ * otherwise all draw the same masks.
+ * kvq_grad_accumulate   with micro read on the device, for every i < n (n >= 1; g KVQ_BF16 or KVQ_F32; g and acc 16-byte aligned):
+ *                           s      = micro == 0 ? (float) g[i] : acc[i] + (float) g[i]
+ *                           acc[i] = micro == A - 1 ? s * (float)(1.0 / A) : s
+ *                       The first micro-step of a cycle STORES and does not read acc: a NaN left by a skipped cycle, or memory
+ *                       never written, does not survive, and no memset is needed.  The last one leaves the mean, which
+ *                       kvq_adam_step_* (grad_scale 1) and kvq_grad_sumsq_partial read as a KVQ_F32 gradient.  The add and the
+ *                       multiply are two roundings, never an FMA.  Elementwise, no atomics: deterministic.  A = 1: acc = g.
+ * kvq_accum_advance     one thread: tick += 1, micro = micro + 1 == A ? 0 : micro + 1.  Once per micro-step, behind its last
+ *                       kvq_grad_accumulate (and behind Adam on the last micro-step of a cycle).
+ * Both are plain kernel launches on `stream`: a captured step replays them unchanged.  A null pointer, n < 1, A < 1 or another
+ * dtype is refused before any launch. */
+int kvq_grad_accumulate(const void* g, int64_t n, int grad_dtype, float* acc, const void* accum_state, int A, void* stream);
+int kvq_accum_advance(void* accum_state, int A, void* stream);
+
 /* ---- codebook revival: a dead code restarts from an encoder output of the current batch (csrc/kvq_vq_revive.hip) -------------
  * Extension, absent from the reference, off by default (VectorQuantizer(revive_after=T)).  State per quantiser, device memory:
  *     idle [G, K] int32, zero-initialised: consecutive TRAINING steps in which code k of codebook g won no token

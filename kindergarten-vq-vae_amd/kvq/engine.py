@@ -172,7 +172,7 @@ class FlatParams:
         # engine_of(model)) never touches them -- 2.5 of the 4.5 GB of flat buffers at bert-base.  The first training steps run
         # eagerly, so the allocation never falls inside a hipGraph capture.
         self._device, self._amsgrad = device, amsgrad
-        self._grad = self._m = self._v = self._vmax = None
+        self._grad = self._m = self._v = self._vmax = self._acc = None
         # contiguous trainable ranges (Adam is launched once per range; one range in `full` mode)
         self.ranges: List[Tuple[int, int]] = []
         for name, p, padded in entries:
@@ -220,6 +220,11 @@ class FlatParams:
     def vmax(self):
         return self._lazy("_vmax", torch.float32) if self._amsgrad else None
 
+    @property
+    def acc(self):
+        """f32 sum / mean of the micro-batch gradients (TrainEngine(grad_accum > 1) only: nothing else touches it)."""
+        return self._lazy("_acc", torch.float32)
+
     def optimizer_state_allocated(self) -> bool:
         return self._grad is not None or self._m is not None or self._v is not None
 
@@ -266,9 +271,10 @@ class _StepGraphs:
     Replay = graph, interlude, graph, ...: ~3 host launches per step on one GPU instead of ~800.  Nothing inside the graphs
     depends on host values that change between steps: see the device step state in include/kvq.h."""
 
-    def __init__(self, eng, ids, mask, dec=None):
+    def __init__(self, eng, ids, mask, dec=None, final=True):
         self.eng = eng
         dev = eng.dev
+        self.final = final      # grad_accum > 1: False = a micro chain (forward, backward, accumulate, advance), True = the same plus the optimiser
         # static input buffers the captured kernels read: ids | mask | ids sorted (stable, pads under -1) | their order
         # [| the decoder's own ids | mask | sorted | order | the loss target -- a Bagon step, models/bagon/Trainer.py:65-130]
         self.pack = eng.pack_batch(ids, mask, *(dec or ())).reshape(-1)
@@ -303,17 +309,18 @@ class _StepGraphs:
                     dkw = dict(dec_ids=self.dec[0], dec_mask=self.dec[1], target_ids=self.dec[4]) if self.dec else {}
                     self.out = eng.forward_backward(self.ids, self.mask, training=eng.model.training, compute_grads=True, **dkw)
                     self.fp8_bwd = (eng.fp8_bwd_launches, list(eng.fp8_bwd_sites))      # what THIS chain holds: restored by every replay
-                    eng.optimizer_step()
+                    eng._finish_step(final)
                     self.graphs[-1].capture_end()
-                    if eng._guard is not None:      # grad_norm / grad_clip_coef: views of the guard state, run() hands out copies
+                    if eng._guard is not None and final:      # grad_norm / grad_clip_coef: views of the guard state, run() hands out copies
                         self.out.update(eng._guard_out)
-                    if eng.revive_after is not None:
+                    if eng.revive_after is not None and final:
                         self.out["codes_revived"] = eng._rv_counter[0]
                     ok = True
                 finally:
                     eng._cap = None
                     eng._prepared = None
                     eng._step_host = step0      # capturing ran no captured kernel: the device step state did not move either
+                                                # (nor the accumulation state: its host mirror is train_step's alone)
                     if not ok:                  # close the capture that was open when the error struck
                         try:
                             self.graphs[-1].capture_end()
@@ -370,7 +377,7 @@ class _StepGraphs:
             g.replay()
             if i < len(self.inter):
                 self.inter[i]()
-        self.eng._step_host += 1
+        self.eng._step_host += int(self.final)
         # the graph's buffers are overwritten by the next step: hand out copies (the four scalars as views of ONE copy)
         sc = self.scal.clone()
         res = {}
@@ -387,14 +394,26 @@ class _StepGraphs:
 class TrainEngine:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
                  milestones=None, gamma=0.1, loss_recon_scale=1.0, loss_vq_scale=1.0, seed=1234,
-                 bucket_mib=64, process_group=None, fp8_forward=None, fp8_backward=None, max_grad_norm=None):
+                 bucket_mib=64, process_group=None, fp8_forward=None, fp8_backward=None, max_grad_norm=None, grad_accum=None):
         self.model = model
+        self.grad_accum = self.check_grad_accum(grad_accum, env=True)
         self.max_grad_norm = self.check_max_grad_norm(max_grad_norm, env=True)     # (before anything is laid out: a bad value changes nothing)
         # option, off by default: codebook revival.  The quantiser's revive_after; None there: KVQ_VQ_REVIVE_AFTER
         # from the environment, as max_grad_norm reads KVQ_MAX_GRAD_NORM (unset / empty: off).  A model without a quantiser ignores it.
         self.revive_after = None
         if hasattr(model, "vector_quantizer"):
             self.revive_after = check_revive_after(getattr(model.vector_quantizer, "revive_after", None), env=True)
+        if self.grad_accum > 1:           # refused before anything is laid out; each combination is a piece of work of its own
+            if process_group is not None or os.environ.get("KVQ_DP_SINGLE_RANK", "0") == "1" \
+                    or (dist.is_initialized() and dist.get_world_size(process_group) > 1):
+                raise KvqError("TrainEngine: grad_accum > 1 with data parallelism (a process group / KVQ_DP_SINGLE_RANK): the gradient "
+                               "exchange would have to move to the accumulator and run on the last micro-step only")
+            if self.revive_after is not None:
+                raise KvqError("TrainEngine: grad_accum > 1 with codebook revival (revive_after / KVQ_VQ_REVIVE_AFTER): the usage "
+                               "flags would have to be OR-ed over the micro-steps of a cycle")
+            if getattr(getattr(model, "vector_quantizer", None), "ema_decay", None) is not None:
+                raise KvqError("TrainEngine: grad_accum > 1 with an EMA codebook (ema_decay): its statistics would have to be summed "
+                               "over the micro-steps of a cycle")
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise KvqError("TrainEngine needs the model on an MI355X (there is no CPU path)")
@@ -609,6 +628,19 @@ class TrainEngine:
             self._guard = nnops.new_grad_guard(dev)
             f = self._guard[1:2].view(torch.float32)
             self._guard_out = dict(grad_norm=f[0], grad_clip_coef=f[1])      # views: train_step hands out copies
+        # option, off by default: gradient accumulation.  grad_accum = A > 1: every train_step call is a
+        # MICRO-step -- forward, backward, flat gradient added into an f32 accumulator (kvq_grad_accumulate) -- and every A-th call
+        # also runs the optimiser on the mean of the A gradients: (loss / A).backward() A times, opt.step() once.  None:
+        # KVQ_GRAD_ACCUM from the environment, as max_grad_norm reads KVQ_MAX_GRAD_NORM (unset / empty: 1).  A = 1: no buffer, no
+        # launch added, today's step and graphs.  The position inside a cycle lives on the device (include/kvq.h "gradient
+        # accumulation"); the dropout seeds follow its micro-step count instead of the optimiser step count, which stands still
+        # inside a cycle.  (The combinations refused at the top of the constructor are each a piece of work of their own.)
+        self._acc_state, self._seed_state, self._accum_host, self._grads_are_mean = None, self._state, 0, False
+        if self.grad_accum > 1:
+            self._acc_state = self._seed_state = nnops.new_accum_state(dev)
+            for a in self.aux:
+                if a["p"].requires_grad:
+                    a["acc"] = torch.zeros_like(a["p"].data)
         # fp8 input-gradient GEMMs of the last training step and their weight keys in launch order: counted while the step is
         # scheduled (eagerly, or at capture -- a replay restores the counts of the graphs it replays)
         self.fp8_bwd_launches = 0
@@ -665,13 +697,30 @@ class TrainEngine:
 
     @property
     def step_count(self):
-        """Optimiser steps applied so far (host mirror of the device step state)."""
+        """Optimiser steps applied so far (host mirror of the device step state).  With grad_accum > 1 a train_step call is a
+        micro-step: this counts the calls that ran the optimiser, as the milestones and Adam's bias corrections do."""
         return self._step_host
 
     @step_count.setter
     def step_count(self, n):
         self._step_host = int(n)
         self._state[0] = int(n)          # lr / bias corrections are recomputed by the next kvq_step_state_advance
+        if self._acc_state is not None:  # n finished cycles: the masks continue where a run of n optimiser steps would be
+            self._acc_state[0] = int(n) * self.grad_accum
+            self._acc_state[1] = 0
+            self._accum_host, self._grads_are_mean = 0, False
+
+    @property
+    def accum_pending(self):
+        """Micro-steps of the current cycle already in the accumulator (host mirror of the device's `micro`; 0 with grad_accum 1)."""
+        return self._accum_host
+
+    def reset_accumulation(self):
+        """Drop a started cycle: the next train_step is the first micro-step of a new one (it stores, so what the accumulator holds
+        does not matter).  The micro-step count `tick` is left alone -- the dropout masks move on."""
+        if self._acc_state is not None:
+            self._acc_state[1] = 0
+        self._accum_host, self._grads_are_mean = 0, False
 
     def _lr_now(self):
         """MultiStepLR ticked once per optimiser step (Trainer.py:114-115): the s-th step (1-based) sees s-1 ticks."""
@@ -1408,7 +1457,10 @@ class TrainEngine:
         self._wg_items, self._wg_keep = [], []
         pre = getattr(self, "_prepared", None) or {}            # this batch's (sorted ids, order) per side: _normalise_prepared()
         self._sorted = {"enc.emb.": pre.get("enc"), "dec.emb.": pre.get("dec") if dec_ids is not None else "enc.emb."}
-        nnops.set_seed_offset(self._state)        # dropout seeds of this engine's launches = _step_seed + device step count
+        # dropout seeds of this engine's launches = _step_seed + device step count (grad_accum > 1: + device micro-step count)
+        nnops.set_seed_offset(self._seed_state)
+        if compute_grads:
+            self._grads_are_mean = False       # the flat gradient is this call's again (train_step says when the accumulator is the mean)
         self._in_fb = True
         try:
             self._q_training = training if quantizer_training is None else bool(quantizer_training)
@@ -1672,7 +1724,8 @@ class TrainEngine:
         self._sorted = resume["sorted_ids"]
         self._g_vq_ext = (g_loss_vq.detach().to(torch.float32).reshape(()) if g_loss_vq is not None
                           else torch.zeros((), dtype=torch.float32, device=self.dev)) if self.has_vq else None
-        nnops.set_seed_offset(self._state)          # the step count has not moved: backward regenerates the forward's dropout masks
+        nnops.set_seed_offset(self._seed_state)     # the step count has not moved: backward regenerates the forward's dropout masks
+        self._grads_are_mean = False
         try:
             with torch.no_grad():
                 try:
@@ -1687,15 +1740,19 @@ class TrainEngine:
 
     def grads_by_parameter(self):
         """{nn.Parameter: float32 gradient} of the last backward, for every trainable parameter of the model (what autograd would
-        have put into .grad): views of the flat bf16 / f32 gradient buffer converted to the parameter's dtype."""
+        have put into .grad): views of the flat bf16 / f32 gradient buffer converted to the parameter's dtype.  grad_accum > 1:
+        after a train_step that ran the optimiser, the mean over the cycle's micro-batches (what Adam read); after any other
+        call, that micro-batch's own gradient."""
         out = {}
+        mean = self._grads_are_mean
         for name, p in self.param_of.items():
             if p.requires_grad:
-                g = self.flat.g(name)
+                o, n, shape = self.flat.seg[name]
+                g = self.flat.acc[o:o + n].view(shape) if mean else self.flat.g(name)
                 out[p] = torch.empty_like(p).copy_(g.reshape(p.shape))           # a copy: the flat buffer is rewritten by the next backward
         for a in self.aux:
             if a["p"].requires_grad:
-                out[a["p"]] = torch.empty_like(a["p"]).copy_(a["g"].reshape(a["p"].shape))
+                out[a["p"]] = torch.empty_like(a["p"]).copy_(a["acc" if mean else "g"].reshape(a["p"].shape))
         return out
 
     def _fb_gen(self, input_ids, attention_mask, training, compute_grads, dec_ids, dec_mask, want_logits, defer, target_ids=None,
@@ -1966,7 +2023,7 @@ class TrainEngine:
         if self.revive_keep_donors:
             self._buf("revive_z", (self.G, zsrc.shape[-2], self.Dg), zsrc.dtype).copy_(zsrc.view(self.G, -1, self.Dg))
             self._rv_donor_shape = ((self.G, zsrc.shape[-2], self.Dg), zsrc.dtype)
-        nnops.set_seed_offset(self._state)
+        nnops.set_seed_offset(self._seed_state)
         try:
             vq_revive_select(zsrc, idx, self._rv_idle, self.E.data, self.revive_after, self._step_seed, used=self._rv_used,
                              rows=self._rv_rows, group=self.group)
@@ -2094,6 +2151,23 @@ class TrainEngine:
             raise KvqError(f"TrainEngine: max_grad_norm must be None, a float > 0 or float('inf'), got {v!r}")
         return float(v)
 
+    @staticmethod
+    def check_grad_accum(v, env=False):
+        """The int >= 1 a TrainEngine(grad_accum=...) accepts (1: off); anything else raises KvqError.  env: None means
+        KVQ_GRAD_ACCUM from the environment (unset or empty: 1).  What grad_accum > 1 may not be combined with is refused by the
+        constructor, which knows the model."""
+        if v is None and env and os.environ.get("KVQ_GRAD_ACCUM", "") != "":
+            try:
+                v = int(os.environ["KVQ_GRAD_ACCUM"])
+            except ValueError:
+                raise KvqError(f"TrainEngine: KVQ_GRAD_ACCUM (grad_accum) must be an integer >= 1, got "
+                               f"{os.environ['KVQ_GRAD_ACCUM']!r}") from None
+        if v is None:
+            return 1
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise KvqError(f"TrainEngine: grad_accum must be None or an integer >= 1, got {v!r}")
+        return v
+
     @property
     def skipped_steps(self):
         """Optimiser steps skipped so far because their gradient was not finite (max_grad_norm only; synchronises)."""
@@ -2102,7 +2176,7 @@ class TrainEngine:
     def _gn_pieces(self, lo, hi):
         """Sum-of-squares launches over the parameter elements of the flat gradient inside [lo, hi): one per contiguous piece, each
         into the next kvq_grad_sumsq_partials() slots of the step's partials buffer."""
-        grad, P = self.flat.grad, self._gn_P
+        grad, P = self._grad_src(), self._gn_P
         for (a, b) in self.flat.pieces:
             a, b = max(a, lo), min(b, hi)
             if a < b:
@@ -2127,23 +2201,54 @@ class TrainEngine:
         P = self._gn_P
         for x in self.aux:
             if x["p"].requires_grad:
-                nnops.grad_sumsq_partial(x["g"].view(-1), self._gn_partials[self._gn_slot * P:(self._gn_slot + 1) * P])
+                nnops.grad_sumsq_partial(x[self._aux_src].view(-1), self._gn_partials[self._gn_slot * P:(self._gn_slot + 1) * P])
                 self._gn_slot += 1
         assert self._gn_slot * P == self._gn_partials.numel(), (self._gn_slot, self._gn_partials.numel())
         nnops.grad_guard_finalize(self._gn_partials, self.max_grad_norm, self._guard)
 
+    def _grad_src(self):
+        """What the optimiser reads as the flat gradient: the buffer backward wrote, or with grad_accum > 1 the f32 mean."""
+        return self.flat.acc if self.grad_accum > 1 else self.flat.grad
+
+    @property
+    def _aux_src(self):
+        return "acc" if self.grad_accum > 1 else "g"
+
+    def _accumulate(self):
+        """grad_accum > 1, behind backward (the queued reductions and weight gradients have been launched): the flat gradient of
+        every trainable range, then the aux gradients, into their accumulators -- store, add, or add and average, as the device's
+        position inside the cycle says."""
+        fl, A = self.flat, self.grad_accum
+        for (a, b) in fl.ranges:
+            nnops.grad_accumulate(fl.grad[a:b], fl.acc[a:b], self._acc_state, A)
+        for x in self.aux:
+            if x["p"].requires_grad:
+                nnops.grad_accumulate(x["g"].view(-1), x["acc"].view(-1), self._acc_state, A)
+
+    def _finish_step(self, final=True):
+        """What follows forward and backward in a train_step.  grad_accum 1: the optimiser.  grad_accum > 1: accumulate, the
+        optimiser on the cycle's last micro-step (`final`), then the device's position moves on."""
+        if self.grad_accum == 1:
+            self.optimizer_step()
+            return
+        self._accumulate()
+        if final:
+            self.optimizer_step()
+        nnops.accum_advance(self._acc_state, self.grad_accum)
+
     def _adam_ranges(self, lo, hi):
         fl = self.flat
         b1, b2 = self.betas
+        grad = self._grad_src()
         for (a, b) in fl.ranges:
             a, b = max(a, lo), min(b, hi)
             if a < b and self.fp8 and self._w8_in_adam:
                 if a % 8 or b % 8:           # (segments and chunk cuts are multiples of 16: cannot happen; a silent fallback would
                     raise KvqError(f"TrainEngine: Adam range [{a}, {b}) is not 8-aligned")       # leave the fp8 mirror stale)
                 # the update also writes the fp8 mirror of the GEMM weights in [a, b) (scales of the last refresh)
-                args = (fl.master[a:b].data_ptr(), fl.grad[a:b].data_ptr(), fl.m[a:b].data_ptr(), fl.v[a:b].data_ptr(),
+                args = (fl.master[a:b].data_ptr(), grad[a:b].data_ptr(), fl.m[a:b].data_ptr(), fl.v[a:b].data_ptr(),
                         fl.vmax[a:b].data_ptr() if fl.vmax is not None else None, fl.shadow[a:b].data_ptr(), b - a,
-                        nnops.io_dtype_of(fl.grad), self._state.data_ptr(), b1, b2, self.eps, self.wd, 1.0,
+                        nnops.io_dtype_of(grad), self._state.data_ptr(), b1, b2, self.eps, self.wd, 1.0,
                         self._w8.data_ptr(), self._w8_span.data_ptr(), self._w8_scale.data_ptr(),
                         self._w8_off.data_ptr(), self._w8_n.data_ptr(), len(self._w8_index), a)
                 if self._guard is not None:
@@ -2151,7 +2256,7 @@ class TrainEngine:
                 else:
                     check(lib().kvq_adam_step_dev_fp8(*args, stream_ptr()), "kvq_adam_step_dev_fp8")
             elif a < b:
-                nnops.adam_step_dev(fl.master[a:b], fl.grad[a:b], fl.m[a:b], fl.v[a:b], self._state, b1, b2, self.eps, self.wd,
+                nnops.adam_step_dev(fl.master[a:b], grad[a:b], fl.m[a:b], fl.v[a:b], self._state, b1, b2, self.eps, self.wd,
                                     vmax=fl.vmax[a:b] if fl.vmax is not None else None,
                                     shadow=fl.shadow[a:b] if fl.shadow is not fl.master else None, guard=self._guard)
 
@@ -2197,7 +2302,7 @@ class TrainEngine:
         b1, b2 = self.betas
         for a in self.aux:
             if a["p"].requires_grad:
-                nnops.adam_step_dev(a["p"].data.view(-1), a["g"].view(-1), a["m"].view(-1), a["v"].view(-1), self._state,
+                nnops.adam_step_dev(a["p"].data.view(-1), a[self._aux_src].view(-1), a["m"].view(-1), a["v"].view(-1), self._state,
                                     b1, b2, self.eps, self.wd, vmax=a["vmax"].view(-1) if a["vmax"] is not None else None,
                                     guard=self._guard)
 
@@ -2323,15 +2428,38 @@ class TrainEngine:
             out = self.forward_backward(input_ids, attention_mask, training=self.model.training, compute_grads=True, **dkw)
         finally:
             self._prepared = None
-        self.optimizer_step()
-        if self._guard is not None:            # copies: the guard state is rewritten by the next step
+        final = self.finish_step()
+        if self._guard is not None and final:  # copies: the guard state is rewritten by the next step
             out.update({k: v.clone() for k, v in self._guard_out.items()})
-        if self.revive_after is not None:      # counter.last (its upper word is padding: 0), rewritten by the next step
+        if self.revive_after is not None and final:      # counter.last (its upper word is padding: 0), rewritten by the next step
             out["codes_revived"] = self._rv_counter[0].clone()
+        out["optimizer_step"] = final
         return out
 
+    def _accum_final(self):
+        """True when the micro-step about to run is the last of its cycle (always, with grad_accum 1)."""
+        return self._accum_host == self.grad_accum - 1
+
+    def _accum_note(self, final):
+        """Host bookkeeping behind a finished micro-step (the device moved its own position: kvq_accum_advance)."""
+        if self.grad_accum > 1:
+            self._accum_host = 0 if final else self._accum_host + 1
+            self._grads_are_mean = final
+
+    def finish_step(self):
+        """What train_step runs behind forward_backward(compute_grads=True), for callers that schedule the two halves themselves:
+        the optimiser -- or, with grad_accum > 1, this micro-step's accumulation and the optimiser on the last one of a cycle.
+        Returns whether the optimiser ran."""
+        final = self._accum_final()
+        self._finish_step(final)
+        self._accum_note(final)
+        return final
+
     def train_step(self, input_ids, attention_mask, prepared=None, dec_ids=None, dec_mask=None, target_ids=None):
-        """One optimiser step.  dec_ids / dec_mask / target_ids: the decoder's own input and the loss target of a Bagon step
+        """One optimiser step -- with grad_accum = A > 1 one MICRO-step: forward, backward, the gradient added into the f32
+        accumulator, and on every A-th call the optimiser on the mean of the A gradients (out["optimizer_step"] says whether it
+        ran; grad_norm / grad_clip_coef / codes_revived appear only then).
+        dec_ids / dec_mask / target_ids: the decoder's own input and the loss target of a Bagon step
         (models/bagon/Trainer.py:78-110; default: the autoencoding step, decoder input = target = input_ids).  prepared: see
         _normalise_prepared().  Once a batch shape has been seen twice the step is replayed from a chain of hipGraphs
         (_StepGraphs: the quantiser and, on multi-GPU runs, the RCCL all-reduces stay eager launches between the graphs); the
@@ -2341,7 +2469,11 @@ class TrainEngine:
                 raise KvqError("TrainEngine.train_step: dec_mask without dec_ids")
             dec_ids, dec_mask = input_ids, attention_mask           # a separate target alone: the decoder still reads the encoder's ids
         dec = (dec_ids, dec_mask, target_ids) if dec_ids is not None else None
-        key = (tuple(input_ids.shape), bool(self.model.training), tuple(dec_ids.shape) if dec is not None else None)
+        shape_key = (tuple(input_ids.shape), bool(self.model.training), tuple(dec_ids.shape) if dec is not None else None)
+        # grad_accum > 1: two chains per batch shape -- micro (forward, backward, accumulate, advance; whether it stores or adds is
+        # decided on the device, so one chain serves positions 0 .. A-2) and final (the same plus the optimiser)
+        final = self._accum_final()
+        key = shape_key if self.grad_accum == 1 else shape_key + (final,)
         seen = self._eager_seen.get(key, 0)
         prep = self._normalise_prepared(prepared, input_ids, dec_ids, check_ids=seen < 2)
         if not self.use_graph:
@@ -2350,7 +2482,8 @@ class TrainEngine:
         g = self._graphs.get(key)
         if g is None:
             # warm the workspaces / GEMM plans eagerly first; few shapes only; fp8_backward: its calibration step is eager
-            if seen < 2 or len(self._graphs) >= 4 or (self.fp8_backward and not self._g8_ready):
+            shapes = {k[:3] for k in self._graphs}             # the cap counts batch shapes, not chains
+            if seen < 2 or (len(shapes) >= 4 and shape_key not in shapes) or (self.fp8_backward and not self._g8_ready):
                 self._eager_seen[key] = seen + 1
                 return self._train_step_eager(input_ids, attention_mask, prep, dec)
             try:
@@ -2359,7 +2492,7 @@ class TrainEngine:
                     dec0 = (dv[0], dv[1], dv[4]) if dv is not None else None
                 else:
                     ids0, mask0, dec0 = input_ids, attention_mask, dec
-                g = self._graphs[key] = _StepGraphs(self, ids0, mask0, dec0)
+                g = self._graphs[key] = _StepGraphs(self, ids0, mask0, dec0, final=final)
             except Exception as e:                       # capture is an optimisation: never let it take a run down
                 if os.environ.get("KVQ_GRAPH_STRICT", "0") == "1":      # (tests: a capture that fails is a failure)
                     self._abandon_capture()
@@ -2369,7 +2502,10 @@ class TrainEngine:
                       f"continuing with eager launches", file=sys.stderr, flush=True)
                 self._abandon_capture()
                 return self._train_step_eager(input_ids, attention_mask, prep, dec)
-        return g.run(input_ids, attention_mask, prep, dec)
+        out = g.run(input_ids, attention_mask, prep, dec)
+        self._accum_note(final)
+        out["optimizer_step"] = final
+        return out
 
     def _abandon_capture(self):
         """Leave a failed capture behind in a state from which eager steps can go on (same collectives, same order)."""

@@ -423,8 +423,46 @@ def grad_guard_finalize(partials, max_norm, guard):
           "kvq_grad_guard_finalize")
 
 
+# ---- gradient accumulation (include/kvq.h "gradient accumulation"): f32 sum of the micro-batch gradients, mean on the last one ----
+def new_accum_state(device):
+    """16 zeroed bytes: struct { uint64 tick; uint32 micro, pad; } of include/kvq.h."""
+    return torch.zeros(2, dtype=torch.int64, device=device)
+
+
+def _accum_ptr(state):
+    if not torch.is_tensor(state) or state.dtype != torch.int64 or state.numel() != 2 or not state.is_contiguous():
+        raise KvqError("an accumulation state is new_accum_state()'s tensor (2 x int64)")
+    require_gpu(state)
+    return state.data_ptr()
+
+
+def read_accum_state(state):
+    """(tick, micro) -- synchronises; for tests and TrainEngine's bookkeeping checks."""
+    _accum_ptr(state)
+    raw = state.cpu()
+    return int(raw[0]), int(raw[1]) & 0xFFFFFFFF
+
+
+def grad_accumulate(g, acc, state, A):
+    """acc (f32, as long as g) = g on the first micro-step of a cycle, acc + g on the others, (acc + g) * (1 / A) on the last;
+    the position is read on the device from `state` (new_accum_state).  g: a flat contiguous f32 / bf16 tensor."""
+    require_gpu(g, acc)
+    if not g.is_contiguous() or g.numel() < 1:
+        raise KvqError("grad_accumulate: a contiguous gradient of at least one element required")
+    if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != g.numel():
+        raise KvqError("grad_accumulate: the accumulator is a contiguous float32 tensor of the gradient's length")
+    check(lib().kvq_grad_accumulate(g.data_ptr(), g.numel(), io_dtype_of(g), acc.data_ptr(), _accum_ptr(state), int(A), stream_ptr()),
+          "kvq_grad_accumulate")
+
+
+def accum_advance(state, A):
+    """tick += 1, micro = (micro + 1) mod A, on the device."""
+    check(lib().kvq_accum_advance(_accum_ptr(state), int(A), stream_ptr()), "kvq_accum_advance")
+
+
 def set_seed_offset(step_state):
-    """Dropout-bearing kernels launched from now on use seed + step_state.step (read on the device); None switches it off."""
+    """Dropout-bearing kernels launched from now on use seed + step_state.step (read on the device); None switches it off.  (Any
+    device tensor whose first word is a uint64 count will do: an accumulating engine passes its accumulation state.)"""
     check(lib().kvq_set_seed_offset(step_state.data_ptr() if step_state is not None else None), "kvq_set_seed_offset")
 
 

@@ -56,11 +56,38 @@ def grad_guard_epoch_record(engine, stats_stage_run: dict, n_steps: int, skipped
     """End of a training stage, after its statistics were read (the one synchronisation of the epoch): ({"<stage>/grad_norm": mean
     norm over the applied steps, "<stage>/skipped_steps": steps skipped so far} | None with the option off, steps skipped so far)."""
     total = stats_stage_run.pop("grad_norm_run", None)
+    n_steps = stats_stage_run.get("optimizer_steps_run", n_steps)      # grad_accum > 1: a norm exists per OPTIMISER step, not per call
     if engine is None or getattr(engine, "max_grad_norm", None) is None or total is None:
         return None, skipped_before
     skipped = int(engine.skipped_steps)
     applied = max(n_steps - (skipped - skipped_before), 1)
     return {f"{stage}/grad_norm": float(total) / applied, f"{stage}/skipped_steps": skipped}, skipped
+
+
+# ---- TrainEngine(grad_accum=...): calls of train_step against optimiser steps ------------------------------------------------------
+def optimizer_step_note(stats_stage_run: dict, stats_step: dict):
+    """Count the step if it ran the optimiser ("optimizer_step": the Python bool of train_step's result; a step without the key --
+    evaluation, the autograd path -- is not counted).  Host arithmetic only."""
+    ran = stats_step.get("optimizer_step")
+    if ran is not None:
+        stats_stage_run["optimizer_steps_run"] = stats_stage_run.get("optimizer_steps_run", 0) + int(bool(ran))
+
+
+def optimizer_steps_epoch(stats_stage_run: dict, n_steps: int) -> int:
+    """End of a training stage, behind grad_guard_epoch_record: the optimiser steps of the stage (n_steps, the number of calls,
+    where no step carried the key)."""
+    return int(stats_stage_run.pop("optimizer_steps_run", n_steps))
+
+
+def drop_open_accumulation(engine, console=None) -> int:
+    """End of train(): a cycle of micro-batches that the last epoch left open is dropped (its gradients never reach the weights);
+    one console line says so.  Returns the micro-batches dropped."""
+    n = int(getattr(engine, "accum_pending", 0) or 0) if engine is not None else 0
+    if n:
+        engine.reset_accumulation()
+        if console is not None:
+            console.print(f"    | gradient accumulation: dropped {n} micro-batch(es) of an unfinished cycle of {engine.grad_accum}")
+    return n
 
 
 # ---- revive_after (codebook revival): the codes a training stage restarted, in the trainers' logs ----------------------------------

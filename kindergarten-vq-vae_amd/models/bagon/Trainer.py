@@ -29,7 +29,7 @@ from torch import Tensor, no_grad, save
 
 from common.consts import *  # noqa: F401,F403
 from common.tensor_utils import replace_pct_rand_values
-from kvq.runlog import grad_guard_epoch_record, grad_norm_note
+from kvq.runlog import drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note, optimizer_steps_epoch
 
 
 def _tokenize(batch, tokenizer, add_special_tokens, max_length, device, side):
@@ -93,6 +93,8 @@ def step(device, model, tokenizer_encoder, tokenizer_decoder,
     }
     if engine is not None and "grad_norm" in out:         # TrainEngine(max_grad_norm=...): a device scalar like the others
         stats["grad_norm_step"] = out["grad_norm"]
+    if engine is not None and "optimizer_step" in out:    # grad_accum: whether this call ran the optimiser (a Python bool, no device read)
+        stats["optimizer_step"] = out["optimizer_step"]
     return stats, input_ids_encoder, input_ids_decoder, recon_ids, labels
 
 
@@ -102,6 +104,7 @@ def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batc
     stats_stage_run["metric_acc_run"] += stats_step["metric_acc_step_per_batch"] * n_els_batch * 1e2
     stats_stage_run["padding_tokens_pct_run"] += stats_step["padding_tokens_pct_step"]
     grad_norm_note(stats_stage_run, stats_step)
+    optimizer_step_note(stats_stage_run, stats_step)
     return stats_stage_run
 
 
@@ -271,9 +274,10 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
             wandb_run.log({"epoch": epoch, **guard_rec})
             if console is not None:
                 console.print(f"    | grad_norm: {guard_rec['train/grad_norm']:.6f} | skipped steps: {guard_rec['train/skipped_steps']}")
+        n_opt = optimizer_steps_epoch(run, s)                                             # grad_accum: a cycle left open carries into the next epoch
         # sentences/s of THIS rank's train stage, loop and all (end_of_epoch_stats_update has just turned the device sums into
         # floats: the stage's kernels have finished).  An extra log entry, not one of the reference's keys.
-        wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": s,
+        wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": s, "perf/optimizer_steps": n_opt,
                        "perf/train_sentences_per_s": n / max(_time.perf_counter() - t_stage, 1e-9)})
         end_of_epoch_print(stats_train_run, stats_train_best, console, epoch, True, COLOR_TRAIN, STATS_EMOJI_TRAIN, False)
         wandb_run.log(create_wandb_log_dict(epoch, stats_train_run, "train"))
@@ -288,6 +292,7 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
         if export_checkpoint and is_main:
             checkpoint(stats_val_best, model, run_path, "val")
         hist.append((stats_train_run, stats_val_run))
+    drop_open_accumulation(engine, console)
     if prg is not None:
         prg.stop()
     return hist

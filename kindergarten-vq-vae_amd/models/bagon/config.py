@@ -51,6 +51,7 @@ USE_ENGINE = True               # kvq.engine.TrainEngine (explicit fwd/bwd on fl
 FP8_FORWARD = False             # extension (BASELINE.json configs[4]): forward GEMMs on the fp8 matrix cores -- False | True | "wide" | "all"
 FP8_BACKWARD = False            # option on top of FP8_FORWARD: input-gradient GEMMs on fp8 (e5m2 gradients, transposed e4m3 weights); DESIGN.md section 5
 MAX_GRAD_NORM = None            # None (off) | float > 0 | float("inf"): the engine step clips its gradient by the global norm and skips non-finite steps (inf: measure and skip only); KVQ_MAX_GRAD_NORM; DESIGN.md section 5b
+GRAD_ACCUM_STEPS = 1            # int >= 1: train_step calls (micro-batches) per optimiser step -- the engine sums their gradients in f32 and Adam reads the mean; MILESTONES, engine.step_count and the bias corrections count OPTIMISER steps, perf/train_steps counts calls; KVQ_GRAD_ACCUM; DESIGN.md section 5d
 
 RUNS_DIR = "./runs/Bagon"
 EXPORT_CHECKPOINT = True
@@ -71,6 +72,16 @@ for _k in [k for k in list(globals()) if k.isupper()]:
             globals()[_k] = _v
 if isinstance(MAX_GRAD_NORM, str):       # KVQ_MAX_GRAD_NORM=inf is no python literal; empty = off (as TrainEngine reads the variable)
     MAX_GRAD_NORM = float(MAX_GRAD_NORM) if MAX_GRAD_NORM.strip() else None
+_v = _os.environ.get("KVQ_GRAD_ACCUM", "").strip()      # the variable TrainEngine itself reads; it wins over KVQ_GRAD_ACCUM_STEPS; empty = unset
+if _v:
+    try:
+        GRAD_ACCUM_STEPS = _ast.literal_eval(_v)
+    except (ValueError, SyntaxError):
+        GRAD_ACCUM_STEPS = _v
+if isinstance(GRAD_ACCUM_STEPS, str) and not GRAD_ACCUM_STEPS.strip():
+    GRAD_ACCUM_STEPS = 1
+if isinstance(GRAD_ACCUM_STEPS, bool) or not isinstance(GRAD_ACCUM_STEPS, int) or GRAD_ACCUM_STEPS < 1:
+    raise ValueError(f"GRAD_ACCUM_STEPS (KVQ_GRAD_ACCUM) must be an integer >= 1, got {GRAD_ACCUM_STEPS!r}")
 
 
 def get_config() -> dict:

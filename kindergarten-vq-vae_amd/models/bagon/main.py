@@ -92,12 +92,15 @@ def main():
                              milestones=MILESTONES if LR_SCHEDULER == "MultiStepLR" else None, gamma=GAMMA, bucket_mib=GRAD_BUCKET_MIB,
                              fp8_forward=FP8_FORWARD if FP8_FORWARD else None,       # (None: the KVQ_FP8 environment switch decides)
                              fp8_backward=FP8_BACKWARD if FP8_BACKWARD else None,     # (None: KVQ_FP8_BACKWARD)
-                             max_grad_norm=MAX_GRAD_NORM)                             # (None: off, or KVQ_MAX_GRAD_NORM)
+                             max_grad_norm=MAX_GRAD_NORM,                             # (None: off, or KVQ_MAX_GRAD_NORM)
+                             grad_accum=GRAD_ACCUM_STEPS)                             # (1: off; the configuration has read KVQ_GRAD_ACCUM)
         if TOKEN_CACHE and same_tok:
             for c in caches:
                 c.packed_pad_id = engine.pad_idx if not any_perturb else "off"     # perturbed ids are sorted by the engine itself
     elif world > 1:
         grad_sync = ddp.GradSync(model.parameters(), bucket_mib=GRAD_BUCKET_MIB)
+    if engine is None and GRAD_ACCUM_STEPS > 1:      # the autograd path steps its optimiser per batch: no silent batch of another size
+        raise SystemExit("GRAD_ACCUM_STEPS > 1 (KVQ_GRAD_ACCUM) needs the engine (USE_ENGINE and a model shape it supports)")
 
     console = None
     if is_main:
@@ -107,6 +110,7 @@ def main():
     run_path = f"{RUNS_DIR}/{run_id}"
     run_conf = get_config()
     run_conf.update({"n_params": model.model_params_summary_dict(), "optimizer": str(opt), "run_id": run_id, "world_size": world,
+                     "grad_accum": engine.grad_accum if engine is not None else 1,
                      "max_grad_norm": engine.max_grad_norm if engine is not None else None})     # what the step really runs with
     if is_main:
         os.makedirs(run_path, exist_ok=True)

@@ -24,7 +24,8 @@ import torch
 from torch import Tensor, no_grad, save
 
 from common.consts import *  # noqa: F401,F403  (colours / emoji)
-from kvq.runlog import codes_revived_note, grad_guard_epoch_record, grad_norm_note, revive_epoch_record
+from kvq.runlog import (codes_revived_note, drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note,
+                        optimizer_steps_epoch, revive_epoch_record)
 
 
 def tokenize_batch(batch, tokenizer, tokenizer_add_special_tokens: bool, max_length: int, device):
@@ -59,6 +60,8 @@ def step(device, model, tokenizer, tokenizer_add_special_tokens: bool, opt,
             stats["grad_norm_step"] = out["grad_norm"]
         if "codes_revived" in out:                # revive_after: codes restarted by this step, a device scalar like the others
             stats["codes_revived_step"] = out["codes_revived"]
+        if "optimizer_step" in out:               # grad_accum: whether this call ran the optimiser (a Python bool, no device read)
+            stats["optimizer_step"] = out["optimizer_step"]
         return stats, input_ids, out["recon_ids"]
 
     loss_vq_step, metric_perp_step, _indices, loss_recon_step, acc_step, recon_ids = \
@@ -99,6 +102,7 @@ def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batc
     stats_stage_run["padding_tokens_pct_run"] += stats_step["padding_tokens_pct_step"]
     grad_norm_note(stats_stage_run, stats_step)
     codes_revived_note(stats_stage_run, stats_step)
+    optimizer_step_note(stats_stage_run, stats_step)
     return stats_stage_run
 
 
@@ -260,6 +264,7 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
             wandb_run.log({"epoch": epoch, **guard_rec})
             if console is not None:
                 console.print(f"    | grad_norm: {guard_rec['train/grad_norm']:.6f} | skipped steps: {guard_rec['train/skipped_steps']}")
+        n_opt = optimizer_steps_epoch(run, n_steps)                                       # grad_accum: a cycle left open carries into the next epoch
         revive_rec = revive_epoch_record(engine, run)                                     # revive_after: codes restarted this epoch / so far
         if revive_rec is not None:
             wandb_run.log({"epoch": epoch, **revive_rec})
@@ -267,7 +272,7 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
                 console.print(f"    | codes revived: {revive_rec['train/codes_revived']} | so far: {revive_rec['train/codes_revived_total']}")
         # sentences/s of THIS rank's train stage, loop and all (end_of_epoch_stats_update has just turned the device sums into
         # floats: the stage's kernels have finished).  An extra log entry, not one of the reference's keys.
-        wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": n_steps,
+        wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": n_steps, "perf/optimizer_steps": n_opt,
                        "perf/train_sentences_per_s": n_els / max(_time.perf_counter() - t_stage, 1e-9)})
         end_of_epoch_print(stats_train_run, stats_train_best, console, epoch, True, COLOR_TRAIN, STATS_EMOJI_TRAIN, False)
         wandb_run.log(create_wandb_log_dict(epoch, stats_train_run, "train"))
@@ -283,6 +288,7 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
         if export_checkpoint and is_main:
             checkpoint(stats_val_best, model, run_path, "val")
         history.append((dict(stats_train_run), dict(stats_val_run)))
+    drop_open_accumulation(engine, console)
     return history
 
 

@@ -36,6 +36,7 @@ USE_ENGINE = True                    # kvq.engine.TrainEngine (explicit fwd/bwd 
 FP8_FORWARD = False                  # extension (BASELINE.json configs[4]): forward GEMMs on the fp8 matrix cores -- False | True | "wide" | "all"
 FP8_BACKWARD = False                 # option on top of FP8_FORWARD: input-gradient GEMMs on fp8 (e5m2 gradients, transposed e4m3 weights); DESIGN.md section 5
 MAX_GRAD_NORM = None                 # None (off) | float > 0 | float("inf"): the engine step clips its gradient by the global norm and skips non-finite steps (inf: measure and skip only); KVQ_MAX_GRAD_NORM; DESIGN.md section 5b
+GRAD_ACCUM_STEPS = 1                 # int >= 1: train_step calls (micro-batches) per optimiser step -- the engine sums their gradients in f32 and Adam reads the mean; MILESTONES, engine.step_count and the bias corrections count OPTIMISER steps, perf/train_steps counts calls; KVQ_GRAD_ACCUM; DESIGN.md section 5d
 
 VQ_MODE = "VectorQuantizer"          # VectorQuantizer | GumbelQuantizer | MultiVectorQuantizer (extension: VQ_N_FACTORS codebooks)
 VQ_N_FACTORS = 1                     # MultiVectorQuantizer: codebooks = slices of the encoder output (must divide VQ_E_DIM)
@@ -94,6 +95,16 @@ if isinstance(VQ_REVIVE_AFTER, str) and not VQ_REVIVE_AFTER.strip():      # KVQ_
     VQ_REVIVE_AFTER = None
 if VQ_REVIVE_AFTER is not None and (isinstance(VQ_REVIVE_AFTER, bool) or not isinstance(VQ_REVIVE_AFTER, int) or VQ_REVIVE_AFTER < 1):
     raise ValueError(f"VQ_REVIVE_AFTER (KVQ_VQ_REVIVE_AFTER) must be None or an integer >= 1, got {VQ_REVIVE_AFTER!r}")
+_v = _os.environ.get("KVQ_GRAD_ACCUM", "").strip()      # the variable TrainEngine itself reads; it wins over KVQ_GRAD_ACCUM_STEPS; empty = unset
+if _v:
+    try:
+        GRAD_ACCUM_STEPS = _ast.literal_eval(_v)
+    except (ValueError, SyntaxError):
+        GRAD_ACCUM_STEPS = _v
+if isinstance(GRAD_ACCUM_STEPS, str) and not GRAD_ACCUM_STEPS.strip():
+    GRAD_ACCUM_STEPS = 1
+if isinstance(GRAD_ACCUM_STEPS, bool) or not isinstance(GRAD_ACCUM_STEPS, int) or GRAD_ACCUM_STEPS < 1:
+    raise ValueError(f"GRAD_ACCUM_STEPS (KVQ_GRAD_ACCUM) must be an integer >= 1, got {GRAD_ACCUM_STEPS!r}")
 
 
 def get_config() -> dict:
