@@ -188,6 +188,24 @@ def agree(flag: bool, src: int = 0, process_group=None) -> bool:
     return bool(box[0])
 
 
+def readable_everywhere(path: str, process_group=None) -> bool:
+    """True when EVERY rank can open `path` for reading (an all-reduce of "readable here" with MIN): a training-state file is
+    read by every rank from a shared filesystem, and a rank that does not see it must stop all of them together -- a lone
+    exit would leave the others waiting in their next collective."""
+    try:
+        with open(path, "rb") as fp:
+            fp.read(1)
+        ok = 1
+    except OSError:
+        ok = 0
+    if not dist.is_initialized() or dist.get_world_size(process_group) == 1:
+        return bool(ok)
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(process_group) == "nccl" else torch.device("cpu")
+    flag = torch.tensor([ok], dtype=torch.int32, device=dev)
+    dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=process_group)
+    return bool(flag.item())
+
+
 def gather_lists(items: list, dst: int = 0, process_group=None) -> list:
     """Every rank's list of (picklable) records concatenated in rank order on rank `dst`; the other ranks get []."""
     if not dist.is_initialized() or dist.get_world_size(process_group) == 1:

@@ -2085,6 +2085,8 @@ class TrainEngine:
         return vq.merge(gzg)
 
     def _ema_step(self):
+        if self._cap is not None:          # capture runs an interlude once on the unwritten buffers of graphs that have not run:
+            return                         # that is no training step -- the statistics do not move; the replays (no _cap) do the work
         zs, zdt, ishape = self._ema_shapes
         z, idx = self._buf("ema_z", zs, zdt), self._buf("ema_idx", ishape, torch.int64)
         self.model.vector_quantizer.ema_update(z, idx.view(self.G, -1) if self.G > 1 else idx)
@@ -2333,6 +2335,227 @@ class TrainEngine:
             self._fp8_quantize_weights()
         if getattr(self, "_epack", None) is not None:
             self._E_version = None             # the codebook pack is rebuilt by the next quantiser call
+
+    # ------------------------------------------------------------------------------------------------------------
+    # resumable training: everything that makes step n + 1 follow step n, as plain CPU data.  Off the step's
+    # path: an engine on which neither method is called allocates nothing and launches nothing for them.
+    # ------------------------------------------------------------------------------------------------------------
+    STATE_FORMAT = 1
+
+    def state_fingerprint(self) -> dict:
+        """Everything that changes the bits of a step or the meaning of a buffer, as plain Python values: a state is loaded only
+        into an engine whose fingerprint equals the stored one (load_state_dict refuses, it does not convert)."""
+        fl = self.flat
+        scope = False if not self.fp8 else ("fused" if self._fp8_fused else ("all" if self._fp8_all else "wide"))
+        return {
+            "layout": [[name, int(o), int(n), bool(fl.trainable[name])] for name, (o, n, _) in fl.seg.items()],
+            "flat_n": int(fl.n),
+            "dtype": str(self.dtype),
+            "lr": float(self.lr), "betas": [float(b) for b in self.betas], "eps": float(self.eps), "weight_decay": float(self.wd),
+            "amsgrad": bool(fl._amsgrad), "milestones": [int(m) for m in self.milestones], "gamma": float(self.gamma),
+            "w_recon": self.w_recon, "w_vq": self.w_vq, "seed": self.seed,
+            "grad_accum": int(self.grad_accum), "max_grad_norm": self.max_grad_norm, "revive_after": self.revive_after,
+            "vq_kind": self.vq_kind, "G": int(self.G), "K": getattr(self, "K", None), "Dg": getattr(self, "Dg", None),
+            "vq_ema": bool(self.vq_ema),
+            "aux": [[list(a["p"].shape), bool(a["p"].requires_grad)] for a in self.aux],
+            "fp8": scope, "fp8_backward": bool(self.fp8_backward),
+            "w8_period": int(self._w8_period) if self.fp8 else None, "w8_in_adam": bool(self._w8_in_adam) if self.fp8 else None,
+            "w8_keys": list(self._w8_index) if self.fp8 else [],
+            "world": int(self.world),
+        }
+
+    def _state_slots(self, present) -> dict:
+        """{path: (destination getter, dtype, numel, required)} of every tensor a state may hold for THIS engine.  A getter is
+        called only when the copy happens: the lazily allocated buffers (moments, accumulator) stay unallocated until then.
+        present(path): whether the state at hand holds that entry (decides the optional ones)."""
+        fl, f32, i64 = self.flat, torch.float32, torch.int64
+        slots = {"flat.master": (lambda: fl.master, f32, fl.n, True)}
+        moments = present("flat.m") or present("flat.v")          # all of them or (a state from before the first step) none
+        for k in ("m", "v") + (("vmax",) if fl._amsgrad else ()):
+            slots["flat." + k] = ((lambda k=k: getattr(fl, k)), f32, fl.n, moments)
+        pending = self.grad_accum > 1 and present("host.accum_pending")
+        if self.grad_accum > 1:
+            slots["flat.acc"] = (lambda: fl.acc, f32, fl.n, pending)
+        for i, a in enumerate(self.aux):
+            for k in ("p", "m", "v") + (("vmax",) if a["vmax"] is not None else ()) + (("acc",) if "acc" in a else ()):
+                get = (lambda a=a: a["p"].data) if k == "p" else (lambda a=a, k=k: a[k])
+                slots[f"aux.{i}.{k}"] = (get, a["p"].dtype, a["p"].numel(), pending if k == "acc" else True)
+        slots["structs.state"] = (lambda: self._state, i64, 3, True)
+        if self._acc_state is not None:
+            slots["structs.acc_state"] = (lambda: self._acc_state, i64, 2, True)
+        if self._guard is not None:
+            slots["structs.guard"] = (lambda: self._guard, i64, 4, True)
+        if self.revive_after is not None:
+            slots["structs.revive_idle"] = (lambda: self._rv_idle, torch.int32, self.G * self.K, True)
+            slots["structs.revive_counter"] = (lambda: self._rv_counter, i64, 2, True)
+        if self.vq_kind in ("VectorQuantizer", "MultiVectorQuantizer") and not self.E.requires_grad:
+            # a codebook Adam does not own (EMA, a frozen mode) is in neither the flat buffer nor aux: here, so that the state is whole
+            slots["structs.codebook"] = (lambda: self.E.data, self.E.dtype, self.E.numel(), True)
+        if self.vq_ema:          # likewise the EMA statistics, buffers of the module
+            vq = self.model.vector_quantizer
+            slots["structs.ema_n"] = (lambda: vq.ema_n, vq.ema_n.dtype, vq.ema_n.numel(), True)
+            slots["structs.ema_m"] = (lambda: vq.ema_m, vq.ema_m.dtype, vq.ema_m.numel(), True)
+        if self.fp8:
+            slots["fp8.w8"] = (lambda: self._w8, torch.uint8, fl.n, True)
+            slots["fp8.w8_amax"] = (lambda: self._w8_amax, f32, self._w8_amax.numel(), True)
+            slots["fp8.w8_scale"] = (lambda: self._w8_scale, f32, self._w8_scale.numel(), True)
+            slots["fp8.a8_state"] = (lambda: self._a8_state, f32, self._a8_state.numel(), True)
+            if self.fp8_backward:
+                slots["fp8.g8_state"] = (lambda: self._g8_state, f32, self._g8_state.numel(), True)
+        return slots
+
+    def state_dict(self) -> dict:
+        """The engine's full training state between two train_step calls (an open accumulation cycle included), as a plain dict of
+        CPU tensors and Python scalars / lists / dicts: it survives torch.save and torch.load(weights_only=True).  Device-to-host
+        copies only -- nothing that writes is enqueued, the bits of every later step are what they would have been.  The small
+        device structs travel as raw words, so a state is tied to their layout in include/kvq.h (kvq_version).  flat.grad and
+        flat.shadow are not state (every backward rewrites the first, refresh_shadow() rebuilds the second), nor are the graphs."""
+        fl = self.flat
+        if self._cap is not None or self._in_fb:
+            raise KvqError("TrainEngine.state_dict: called inside a step")
+        pending = self._accum_host > 0
+        flat = {"master": fl.master}
+        for k in ("m", "v", "vmax"):
+            if getattr(fl, "_" + k) is not None:
+                flat[k] = getattr(fl, "_" + k)
+        if pending:
+            flat["acc"] = fl.acc
+        aux = []
+        for a in self.aux:
+            d = {"p": a["p"].data, "m": a["m"], "v": a["v"]}
+            if a["vmax"] is not None:
+                d["vmax"] = a["vmax"]
+            if pending and "acc" in a:
+                d["acc"] = a["acc"]
+            aux.append(d)
+        structs = {"state": self._state}
+        if self._acc_state is not None:
+            structs["acc_state"] = self._acc_state
+        if self._guard is not None:
+            structs["guard"] = self._guard
+        if self.revive_after is not None:
+            structs["revive_idle"], structs["revive_counter"] = self._rv_idle, self._rv_counter
+        if self.vq_kind in ("VectorQuantizer", "MultiVectorQuantizer") and not self.E.requires_grad:
+            structs["codebook"] = self.E.data
+        if self.vq_ema:
+            structs["ema_n"], structs["ema_m"] = self.model.vector_quantizer.ema_n, self.model.vector_quantizer.ema_m
+        cpu = lambda d: {k: v.detach().cpu() for k, v in d.items()}
+        out = {"format": self.STATE_FORMAT, "kvq_version": int(lib().kvq_version()), "fingerprint": self.state_fingerprint(),
+               "flat": cpu(flat), "aux": [cpu(d) for d in aux], "structs": cpu(structs),
+               "host": {"step": int(self._step_host), "accum_pending": int(self._accum_host), "grads_are_mean": bool(self._grads_are_mean)}}
+        if self.fp8:
+            f8 = {"w8": self._w8, "w8_amax": self._w8_amax, "w8_scale": self._w8_scale, "a8_state": self._a8_state}
+            if self.fp8_backward:
+                f8["g8_state"] = self._g8_state
+            out["fp8"] = cpu(f8)
+            if self.fp8_backward:
+                out["fp8"]["g8_ready"], out["fp8"]["g8_live"] = bool(self._g8_ready), sorted(self._g8_live)
+        return out
+
+    @staticmethod
+    def _state_entry(state, path):
+        """state["a"]["b"] / state["aux"][i]["k"] for path "a.b" / "aux.i.k"; None when it is not there."""
+        node = state
+        for part in path.split("."):
+            if isinstance(node, dict):
+                node = node.get(part)
+            elif isinstance(node, (list, tuple)) and part.isdigit() and int(part) < len(node):
+                node = node[int(part)]
+            else:
+                return None
+            if node is None:
+                return None
+        return node
+
+    def load_state_dict(self, state) -> None:
+        """Continue where the engine that wrote `state` (state_dict()) stood.  First every check -- format, kvq_version, the whole
+        fingerprint, presence / dtype / size of every entry -- and a KvqError naming each differing key with both values; a refused
+        load has written nothing.  Then copies INTO the existing buffers: no attribute a captured graph may hold the address of is
+        rebound, an engine that replays graphs keeps replaying them.  Not sync_from_model(): that would re-quantise the fp8 weights
+        with fresh scales in the middle of a scale period."""
+        if self._cap is not None or self._in_fb:
+            raise KvqError("TrainEngine.load_state_dict: called inside a step")
+        if not isinstance(state, dict):
+            raise KvqError(f"TrainEngine.load_state_dict: a state_dict() is a dict, got {type(state).__name__}")
+        short = lambda v: (lambda r: r if len(r) <= 120 else r[:117] + "...")(repr(v))
+        bad = []
+        for key, want in (("format", self.STATE_FORMAT), ("kvq_version", int(lib().kvq_version()))):
+            if key not in state:
+                bad.append(f"{key}: missing")
+            elif state[key] != want or isinstance(state[key], bool):
+                bad.append(f"{key}: state {short(state[key])}, engine {short(want)}")
+        mine, theirs = self.state_fingerprint(), state.get("fingerprint")
+        if not isinstance(theirs, dict):
+            bad.append("fingerprint: missing")
+        elif not bad:
+            for key in sorted(set(mine) | set(theirs)):
+                if key not in theirs or key not in mine:
+                    bad.append(f"fingerprint.{key}: " + ("missing in the state" if key not in theirs else "unknown to this engine"))
+                elif theirs[key] != mine[key]:
+                    a, b = theirs[key], mine[key]
+                    if key == "layout" and isinstance(a, list):          # the first entry that differs says more than two long lists
+                        i = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+                        a = f"{len(a)} entries, [{i}] = {a[i] if i < len(a) else None}"
+                        b = f"{len(b)} entries, [{i}] = {b[i] if i < len(b) else None}"
+                    bad.append(f"fingerprint.{key}: state {short(a)}, engine {short(b)}")
+        if bad:
+            raise KvqError("TrainEngine.load_state_dict: this state does not belong to this engine -- " + "; ".join(bad))
+        host = state.get("host")
+        for key, typ in (("step", int), ("accum_pending", int), ("grads_are_mean", bool)):
+            if not isinstance(host, dict) or not isinstance(host.get(key), typ):
+                bad.append(f"host.{key}: missing")
+        if not bad and not 0 <= host["accum_pending"] < self.grad_accum:
+            bad.append(f"host.accum_pending: state {host['accum_pending']}, engine has cycles of {self.grad_accum}")
+        present = lambda path: bool(self._state_entry(state, path)) if path.startswith("host.") else self._state_entry(state, path) is not None
+        slots = self._state_slots(present)
+        plan = []
+        for path, (get, dtype, numel, required) in slots.items():
+            t = self._state_entry(state, path)
+            if t is None:
+                if required:
+                    bad.append(f"{path}: missing")
+                continue
+            if not torch.is_tensor(t) or t.dtype != dtype or t.numel() != numel:
+                got = f"{t.dtype} x {t.numel()}" if torch.is_tensor(t) else type(t).__name__
+                bad.append(f"{path}: state {got}, engine {dtype} x {numel}")
+                continue
+            plan.append((get, t))
+        if self.fp8_backward:
+            f8 = state.get("fp8") if isinstance(state.get("fp8"), dict) else {}
+            if not isinstance(f8.get("g8_ready"), bool):
+                bad.append("fp8.g8_ready: missing")
+            live = f8.get("g8_live")
+            if not isinstance(live, list) or any(k not in self._g8_index for k in live):
+                bad.append(f"fp8.g8_live: state {short(live)}, engine knows the sites {short(sorted(self._g8_index))}")
+        if bad:
+            raise KvqError("TrainEngine.load_state_dict: this state does not belong to this engine -- " + "; ".join(bad))
+        # ---- from here on the engine is written
+        fl = self.flat
+        with torch.no_grad():
+            for get, t in plan:
+                dst = get()
+                dst.copy_(t.reshape(dst.shape))
+            if present("flat.m") is False and fl.optimizer_state_allocated():       # a state from before the first step: moments restart
+                for k in ("_m", "_v", "_vmax"):
+                    if getattr(fl, k) is not None:
+                        getattr(fl, k).zero_()
+        self._step_host, self._accum_host = int(host["step"]), int(host["accum_pending"])
+        self._grads_are_mean = bool(host["grads_are_mean"])
+        self._rv_pending = False
+        fl.refresh_shadow()
+        if getattr(self, "_epack", None) is not None or hasattr(self, "_E_version"):
+            self._E_version = None                     # the next quantiser call repacks the codebook
+        if self.fp8_backward:
+            ready, live = bool(state["fp8"]["g8_ready"]), set(state["fp8"]["g8_live"])
+            if (ready, live) != (self._g8_ready, self._g8_live):
+                # another set of live sites: another per-step transpose table -- chains captured with the old one are not this state's
+                self._graphs.clear()
+                self._eager_seen.clear()
+                self._g8_ready, self._g8_live = ready, live
+                self._fp8_transpose_table([t for t in self._w8t_sites if t[0] in live] if ready else self._w8t_sites)
+            self._fp8_transpose_weights()
+        # the in-place writes (and a model.load_state_dict before this call) bumped tensor versions: not a write from outside
+        self._param_versions = self._versions()
 
     @staticmethod
     def supports(model, seq_len: int) -> bool:

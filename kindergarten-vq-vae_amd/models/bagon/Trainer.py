@@ -30,6 +30,7 @@ from torch import Tensor, no_grad, save
 from common.consts import *  # noqa: F401,F403
 from common.tensor_utils import replace_pct_rand_values
 from kvq.runlog import drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note, optimizer_steps_epoch
+from kvq.train_state import check_every, restore_trainer, save_train_state, trainer_state
 
 
 def _tokenize(batch, tokenizer, add_special_tokens, max_length, device, side):
@@ -245,7 +246,13 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
           tokenizer_decoder_add_special_tokens, tokenized_decoder_sentence_max_length,
           encoder_perturb_train_pct, encoder_perturb_val_pct, decoder_perturb_train_pct, decoder_perturb_val_pct,
           n_epochs_to_decode_after, decoded_sentences, opt, lr_sched, n_epochs, vocab_size_encoder, vocab_size_decoder,
-          wandb_run, run_path, export_checkpoint=True, grad_sync=None, engine=None, is_main=True):
+          wandb_run, run_path, export_checkpoint=True, grad_sync=None, engine=None, is_main=True,
+          train_state_path=None, train_state_every: int = 1, resume=None, train_state_config=None):
+    """train_state_path: the run's training-state file (kvq.train_state; None: none is written), rewritten at the end of every
+    train_state_every-th epoch and of the last one, behind validation and the best checkpoints.  resume: such a file's dict
+    (load_train_state) -- the loop starts behind its last finished epoch; model and engine / optimiser were loaded by the caller.
+    train_state_config: the run's configuration, stored in the file."""
+    check_every(train_state_every, "train_state_every")
     stats_train_best, stats_val_best = init_stats_best(), init_stats_best()
     step_kw = dict(device=device, model=model, tokenizer_encoder=tokenizer_encoder, tokenizer_decoder=tokenizer_decoder,
                    tokenizer_encoder_add_special_tokens=tokenizer_encoder_add_special_tokens,
@@ -260,7 +267,10 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
                  prg.add_task(f"[bold {COLOR_VAL}] Val   batches", total=n_batches_val))
     hist = []
     skipped = 0
-    for epoch in range(1, n_epochs + 1):
+    first_epoch = 1
+    if resume is not None:
+        first_epoch, stats_train_best, stats_val_best, hist, skipped = restore_trainer(resume, decoded_sentences, dl_train)
+    for epoch in range(first_epoch, n_epochs + 1):
         if prg is not None:
             prg.reset(tasks[0]); prg.reset(tasks[1])
         dec = decoded_sentences if epoch % n_epochs_to_decode_after == 0 else None
@@ -292,6 +302,11 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
         if export_checkpoint and is_main:
             checkpoint(stats_val_best, model, run_path, "val")
         hist.append((stats_train_run, stats_val_run))
+        if train_state_path is not None and (epoch % train_state_every == 0 or epoch == n_epochs):
+            # (before drop_open_accumulation: a cycle the last epoch left open travels in the file and continues in a resumed run)
+            save_train_state(train_state_path, model, trainer_state(epoch, stats_train_best, stats_val_best, hist, skipped,
+                                                                    decoded_sentences, dl_train),
+                             train_state_config or {}, engine=engine, opt=opt, lr_sched=lr_sched, is_main=is_main)
     drop_open_accumulation(engine, console)
     if prg is not None:
         prg.stop()

@@ -29,9 +29,11 @@ from dsentences.dataset import dSentencesDataset  # noqa: E402
 from dsentences.synthetic import write_corpus  # noqa: E402
 from dsentences.token_cache import cache_of_split  # noqa: E402
 from kvq import ddp  # noqa: E402
+from kvq._ffi import KvqError  # noqa: E402
 from kvq.engine import TrainEngine  # noqa: E402
 from kvq.runlog import init_run  # noqa: E402
 from kvq.tokenizer import load_tokenizer  # noqa: E402
+from kvq.train_state import config_differences, load_optimizer, load_train_state, resolve_path  # noqa: E402
 from models.bagon.Bagon import Bagon  # noqa: E402
 from models.bagon.Trainer import test, train  # noqa: E402
 
@@ -102,24 +104,55 @@ def main():
     if engine is None and GRAD_ACCUM_STEPS > 1:      # the autograd path steps its optimiser per batch: no silent batch of another size
         raise SystemExit("GRAD_ACCUM_STEPS > 1 (KVQ_GRAD_ACCUM) needs the engine (USE_ENGINE and a model shape it supports)")
 
+    # RESUME_FROM: continue a run from its training-state file (kvq/train_state.py).  Every rank reads the SAME
+    # file and takes the same decisions from it, so a refusal stops all of them; a rank that cannot read it stops all of them too.
+    state_config = dict(get_config(), ds_gen_seed=DS_GEN_SEED, world_size=world)      # + what decides an epoch's batches besides config.py
+    resume = None
+    if RESUME_FROM is not None:
+        state_file = resolve_path(RESUME_FROM, "bagon_train_state_last.pth")
+        if not ddp.readable_everywhere(state_file):
+            raise SystemExit(f"RESUME_FROM: {state_file} cannot be read on every rank (all ranks read one file: a shared filesystem)")
+        resume = load_train_state(state_file, map_location="cpu")
+        diff = config_differences(resume["config"], state_config)
+        if diff:
+            raise SystemExit("RESUME_FROM: the stored run was configured differently -- " + "; ".join(diff))
+        if (engine is not None) != ("engine" in resume):
+            raise SystemExit(f"RESUME_FROM: the stored run trained {'on the engine' if 'engine' in resume else 'on the autograd path'}, "
+                             f"this one is set up for the other (USE_ENGINE)")
+        model.load_state_dict(resume["model_state_dict"])
+        if engine is not None:
+            try:
+                engine.load_state_dict(resume["engine"])
+            except KvqError as e:
+                raise SystemExit(f"RESUME_FROM: {e}") from None
+        else:
+            load_optimizer(resume, opt, lr_sched)
+
     console = None
     if is_main:
         from rich.console import Console
         console = Console()
     run_id = ddp.same_everywhere(datetime.now().strftime(RUN_ID_TIMESTAMP_FORMAT))     # one run directory for all ranks
     run_path = f"{RUNS_DIR}/{run_id}"
+    if resume is not None:                    # the resumed run goes on in the stored run's directory, under its id
+        run_path = os.path.dirname(os.path.abspath(state_file))
+        run_id = resume["config"].get("run_id") or os.path.basename(run_path)
+    state_config["run_id"] = run_id
     run_conf = get_config()
     run_conf.update({"n_params": model.model_params_summary_dict(), "optimizer": str(opt), "run_id": run_id, "world_size": world,
                      "grad_accum": engine.grad_accum if engine is not None else 1,
                      "max_grad_norm": engine.max_grad_norm if engine is not None else None})     # what the step really runs with
     if is_main:
         os.makedirs(run_path, exist_ok=True)
-        with open(f"{run_path}/run_conf.json", "w") as fp:
-            json.dump(run_conf, fp)
+        if resume is None:                    # (a resumed run leaves the stored run's run_conf.json as it is)
+            with open(f"{run_path}/run_conf.json", "w") as fp:
+                json.dump(run_conf, fp)
     wandb_run = init_run(WANDB_PROJECT_NAME, WANDB_GROUP, WANDB_JOB_TYPE, run_conf, WANDB_MODE if is_main else "disabled",
                          run_path if is_main else None)
 
     decoded = []
+    if resume is not None:
+        wandb_run.log({"resumed_after_epoch": resume["trainer"]["epoch"]})
     common = dict(tokenizer_encoder=tok_enc, tokenizer_decoder=tok_dec,
                   tokenizer_encoder_add_special_tokens=TOKENIZER_ADD_SPECIAL_TOKENS,
                   tokenized_encoder_sentence_max_length=TOKENIZED_SENTENCE_MAX_LENGTH,
@@ -131,7 +164,9 @@ def main():
           model=model, n_epochs_to_decode_after=N_EPOCHS_TO_DECODE_AFTER, decoded_sentences=decoded, opt=opt, lr_sched=lr_sched,
           n_epochs=N_EPOCHS, encoder_perturb_train_pct=ENCODER_PERTURB_TRAIN_PCT, encoder_perturb_val_pct=ENCODER_PERTURB_VAL_PCT,
           decoder_perturb_train_pct=DECODER_PERTURB_TRAIN_PCT, decoder_perturb_val_pct=DECODER_PERTURB_VAL_PCT, wandb_run=wandb_run,
-          run_path=run_path, export_checkpoint=EXPORT_CHECKPOINT, grad_sync=grad_sync, engine=engine, is_main=is_main, **common)
+          run_path=run_path, export_checkpoint=EXPORT_CHECKPOINT, grad_sync=grad_sync, engine=engine, is_main=is_main,
+          train_state_path=f"{run_path}/bagon_train_state_last.pth" if EXPORT_TRAIN_STATE else None,
+          train_state_every=TRAIN_STATE_EVERY_EPOCHS, resume=resume, train_state_config=state_config, **common)
     # The test stage runs on EVERY rank (each on its shard of the test split): test() ends in the stage's all-reduce of the
     # statistics (Trainer._sum_over_ranks), a collective every rank has to enter.  Rank 0 wrote the checkpoint; agree() puts a
     # barrier behind that write and hands every rank rank 0's answer to "is there a best checkpoint".

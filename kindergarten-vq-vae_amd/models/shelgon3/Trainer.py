@@ -26,6 +26,7 @@ from torch import Tensor, no_grad, save
 from common.consts import *  # noqa: F401,F403  (colours / emoji)
 from kvq.runlog import (codes_revived_note, drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note,
                         optimizer_steps_epoch, revive_epoch_record)
+from kvq.train_state import check_every, restore_trainer, save_train_state, trainer_state
 
 
 def tokenize_batch(batch, tokenizer, tokenizer_add_special_tokens: bool, max_length: int, device):
@@ -232,7 +233,12 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
           loss_recon_rescale_factor: float, loss_recon_weight: float, loss_vq_rescale_factor: float, loss_vq_weight: float,
           loss_perp_rescale_factor: float, loss_perp_weight: float, lr_sched, n_epochs: int, vocab_size: int,
           wandb_run, run_path: str, export_checkpoint: bool, max_length: int = 12, grad_sync=None, is_main: bool = True,
-          engine=None):
+          engine=None, train_state_path=None, train_state_every: int = 1, resume=None, train_state_config=None):
+    """train_state_path: the run's training-state file (kvq.train_state; None: none is written), rewritten at the end of every
+    train_state_every-th epoch and of the last one, behind validation and the best checkpoints.  resume: such a file's dict
+    (load_train_state) -- the loop starts behind its last finished epoch; model and engine / optimiser were loaded by the caller.
+    train_state_config: the run's configuration, stored in the file."""
+    check_every(train_state_every, "train_state_every")
     if not export_checkpoint and console is not None:
         console.print(f"[bold {COLOR_WARNING}]Warning[/bold {COLOR_WARNING}] checkpoint exporting is [bold {COLOR_OFF}]OFF[/bold {COLOR_OFF}]!\n")
     weights = dict(loss_recon_rescale_factor=loss_recon_rescale_factor, loss_recon_weight=loss_recon_weight,
@@ -247,7 +253,10 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
     stats_train_best, stats_val_best = init_stats_best(), init_stats_best()
     history = []
     skipped = 0
-    for epoch in range(1, n_epochs + 1):
+    first_epoch = 1
+    if resume is not None:
+        first_epoch, stats_train_best, stats_val_best, history, skipped = restore_trainer(resume, decoded_sentences, dl_train)
+    for epoch in range(first_epoch, n_epochs + 1):
         if tasks:
             prg.reset(tasks[1]); prg.reset(tasks[2])
         decode_now = decoded_sentences if epoch % n_epochs_to_decode_after == 0 else None
@@ -288,6 +297,11 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
         if export_checkpoint and is_main:
             checkpoint(stats_val_best, model, run_path, "val")
         history.append((dict(stats_train_run), dict(stats_val_run)))
+        if train_state_path is not None and (epoch % train_state_every == 0 or epoch == n_epochs):
+            # (before drop_open_accumulation: a cycle the last epoch left open travels in the file and continues in a resumed run)
+            save_train_state(train_state_path, model, trainer_state(epoch, stats_train_best, stats_val_best, history, skipped,
+                                                                    decoded_sentences, dl_train),
+                             train_state_config or {}, engine=engine, opt=opt, lr_sched=lr_sched, is_main=is_main)
     drop_open_accumulation(engine, console)
     return history
 

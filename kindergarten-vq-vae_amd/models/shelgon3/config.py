@@ -74,6 +74,9 @@ GRAD_BUCKET_MIB = 64                 # gradient all-reduce bucket size (multi-GP
 # --- run / logging --------------------------------------------------------------------------------------------------
 RUNS_DIR = "./runs/Shelgon"
 EXPORT_CHECKPOINT = True
+EXPORT_TRAIN_STATE = False           # write <run dir>/shelgon_train_state_last.pth (kvq/train_state.py): model, the engine's full training state (or optimiser + scheduler), the trainer's bookkeeping and the generators -- what RESUME_FROM continues from, bit for bit on the engine path; DESIGN.md section 5e
+TRAIN_STATE_EVERY_EPOCHS = 1         # int >= 1: the file is rewritten at the end of every this-many-th epoch and of the last one (a save is a device-to-host copy of the flat buffers: profiles/train_state.md has its cost beside an epoch's)
+RESUME_FROM = None                   # None | a run directory or a training-state file: continue that run IN ITS directory at the epoch behind the stored one; N_EPOCHS is the new total, the batch-deciding constants and the engine's options must be the stored ones (refused otherwise)
 WANDB_SILENT = "true"
 WANDB_PROJECT_NAME = "kindergarten-vq-vae"
 WANDB_GROUP = "Shelgon"
@@ -105,6 +108,14 @@ if isinstance(GRAD_ACCUM_STEPS, str) and not GRAD_ACCUM_STEPS.strip():
     GRAD_ACCUM_STEPS = 1
 if isinstance(GRAD_ACCUM_STEPS, bool) or not isinstance(GRAD_ACCUM_STEPS, int) or GRAD_ACCUM_STEPS < 1:
     raise ValueError(f"GRAD_ACCUM_STEPS (KVQ_GRAD_ACCUM) must be an integer >= 1, got {GRAD_ACCUM_STEPS!r}")
+if isinstance(TRAIN_STATE_EVERY_EPOCHS, bool) or not isinstance(TRAIN_STATE_EVERY_EPOCHS, int) or TRAIN_STATE_EVERY_EPOCHS < 1:
+    raise ValueError(f"TRAIN_STATE_EVERY_EPOCHS (KVQ_TRAIN_STATE_EVERY_EPOCHS) must be an integer >= 1, got {TRAIN_STATE_EVERY_EPOCHS!r}")
+if isinstance(RESUME_FROM, str) and not RESUME_FROM.strip():      # KVQ_RESUME_FROM= (empty) = unset
+    RESUME_FROM = None
+if RESUME_FROM is not None and not isinstance(RESUME_FROM, str):
+    raise ValueError(f"RESUME_FROM (KVQ_RESUME_FROM) must be None or the path of a run directory / training-state file, got {RESUME_FROM!r}")
+if not isinstance(EXPORT_TRAIN_STATE, bool):
+    raise ValueError(f"EXPORT_TRAIN_STATE (KVQ_EXPORT_TRAIN_STATE) must be True or False, got {EXPORT_TRAIN_STATE!r}")
 
 
 def get_config() -> dict:
