@@ -486,7 +486,8 @@ int kvq_fp8_transpose_segments(const void* src8, void* dst8, const int64_t* src_
 
 /* torch.optim.Adam step (models/shelgon3/main.py:91: lr, weight_decay (L2, coupled), amsgrad) on flat buffers.
  *   p, m, v [, vmax] f32; g grad_dtype (scaled by grad_scale first); shadow_bf16 (may be NULL) receives bf16(p_new).
- *   step >= 1 is the 1-based step count for bias correction.  Any n >= 1 (16-byte aligned buffers; the last n %% 4 elements take a
+ *   step >= 1 is the 1-based step count for bias correction (1 - beta1^step and sqrt(1 - beta2^step) are formed in double and
+ *   rounded to f32 once, as kvq_step_state_advance forms them).  Any n >= 1 (16-byte aligned buffers; the last n %% 4 elements take a
  *   scalar path: the 9-code Gumbel bias of the reference's analysis run). */
 /* kvq_adam_step_dev that also writes the fp8 (e4m3) mirror of the GEMM weights inside [first_element, first_element + n) of the flat
  * parameter buffer: w8_mirror is indexed like that buffer (one byte per element), span_segment[element >> 11] = the quantisation

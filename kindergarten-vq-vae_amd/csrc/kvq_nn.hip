@@ -2951,8 +2951,10 @@ int kvq_adam_step(float* p, const void* g, float* m, float* v, float* vmax, void
                   float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale,
                   void* stream) {
     KVQ_REQUIRE(step >= 1, "kvq_adam_step: step >= 1");
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+    // in double and rounded once, as step_state_advance_kernel does it: 1.0f - powf(beta2, step) loses 55 f32 ulps of bc2s at
+    // beta2 = 0.999, step 2 (the power rounds to f32 next to 1 and the difference keeps that absolute error)
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     return adam_launch(p, g, m, v, vmax, shadow_bf16, n, grad_dtype, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, nullptr, stream);
 }
 
