@@ -584,6 +584,33 @@ int kvq_adam_step_guarded_fp8(float* p, const void* g, float* m, float* v, float
 int kvq_grad_accumulate(const void* g, int64_t n, int grad_dtype, float* acc, const void* accum_state, int A, void* stream);
 int kvq_accum_advance(void* accum_state, int A, void* stream);
 
+/* ---- exponential moving average of the trained weights (csrc/kvq_weight_ema.hip) ----------------------------------------------
+ * Extension, off by default (TrainEngine(weight_ema=decay)): beside the f32 master copy of every parameter Adam owns, an f32
+ * average of what the optimiser left there, updated behind Adam inside the step; evaluation and the best-val checkpoints run under
+ * it (TrainEngine.weight_ema_applied()).
+ * weight-EMA state: 16 bytes of device memory, 8-byte aligned, zero-initialised:
+ *     struct { uint64_t updates; float last_decay; uint32_t pad; }
+ * updates counts the updates applied (a skipped step applies none); last_decay is the d of the last applied one, 0 for the first.
+ * kvq_weight_ema_update   with t = updates read on the device, for every i < n (n >= 1; p and ema 16-byte aligned, disjoint):
+ *                             t == 0:  ema[i] = p[i]                                  (a STORE: ema is not read)
+ *                             t >= 1:  d = min((double) decay, (1.0 + t) / (10.0 + t))
+ *                                      ema[i] = (float)(d * (double) ema[i] + (1.0 - d) * (double) p[i])
+ *                         The first update does not read ema: memory never written, or a NaN, does not survive, and no memset is
+ *                         needed (the idiom of kvq_grad_accumulate's first micro-step).  Every f64 operation is rounded on its own,
+ *                         never an FMA, and the sum is rounded once to f32.  Elementwise, no atomics: deterministic.
+ * kvq_weight_ema_advance  one thread: last_decay = t == 0 ? 0 : (float) d, then updates = t + 1.  Once per optimiser step, behind
+ *                         its last kvq_weight_ema_update.
+ * guard (both; may be NULL): the step's gradient guard state.  With guard->skip set the kernel returns before its first store, as
+ *                         kvq_adam_step_guarded* do: the weights did not move, neither does their average nor the state.
+ * kvq_weight_ema_swap     p[i] <-> ema[i] for every i < n, exactly (a second call restores every bit), and, where shadow_bf16 is
+ *                         not NULL (8-byte aligned), shadow_bf16[i] = bf16(the new p[i]) with the rounding of the Adam kernels'
+ *                         shadow store (nearest even, a NaN stays a NaN).  p == ema or overlapping buffers are refused.
+ * All three are plain kernel launches on `stream`: a captured step replays them unchanged.  A null pointer, n < 1, decay outside
+ * (0, 1) or a misaligned pointer is refused before any launch. */
+int kvq_weight_ema_update(const float* p, float* ema, int64_t n, float decay, const void* ema_state, const void* guard, void* stream);
+int kvq_weight_ema_advance(void* ema_state, float decay, const void* guard, void* stream);
+int kvq_weight_ema_swap(float* p, float* ema, void* shadow_bf16, int64_t n, void* stream);
+
 /* ---- codebook revival: a dead code restarts from an encoder output of the current batch (csrc/kvq_vq_revive.hip) -------------
  * Extension, absent from the reference, off by default (VectorQuantizer(revive_after=T)).  State per quantiser, device memory:
  *     idle [G, K] int32, zero-initialised: consecutive TRAINING steps in which code k of codebook g won no token

@@ -140,6 +140,9 @@ SIGNATURES = {
     "kvq_vq_revive_apply": (_int, [_vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kvq_grad_accumulate": (_int, [_vp, _i64, _int, _vp, _vp, _int, _vp]),
     "kvq_accum_advance": (_int, [_vp, _int, _vp]),
+    "kvq_weight_ema_update": (_int, [_vp, _vp, _i64, _f32, _vp, _vp, _vp]),
+    "kvq_weight_ema_advance": (_int, [_vp, _f32, _vp, _vp]),
+    "kvq_weight_ema_swap": (_int, [_vp, _vp, _vp, _i64, _vp]),
     "kvq_embed_grad_workspace_bytes": (_sz, [_i64, _int]),
     "kvq_embed_grad": (_int, [_vp, _vp, _vp, _i64, _int, _i64, _int, _vp, _int, _int, _vp, _sz, _vp]),
     "kvq_dropout": (_int, [_vp, _i64, _f32, C.c_uint64, C.c_uint32, _int, _vp, _vp]),
@@ -187,7 +190,7 @@ def lib():
 # ---- per-family kernel time (bench.py): event pairs around every entry point of a few EAGER steps -------------------------------
 _FAMILIES = (("kvq_gemm_", "gemm"), ("kvq_attn_", "attention"), ("kvq_dropout_residual_ln", "layernorm"), ("kvq_ln_", "layernorm"),
              ("kvq_embed_ln_fwd", "layernorm"), ("kvq_ce_", "loss"), ("kvq_seq_acc", "loss"), ("kvq_adam_", "adam"),
-             ("kvq_step_state_", "adam"), ("kvq_grad_", "adam"), ("kvq_accum_", "adam"), ("kvq_vq_", "vq"), ("kvq_gumbel_", "vq"), ("kvq_fp8_", "fp8_quantize"), ("kvq_reduce_batch", "reduce"),
+             ("kvq_step_state_", "adam"), ("kvq_grad_", "adam"), ("kvq_accum_", "adam"), ("kvq_weight_ema_", "adam"), ("kvq_vq_", "vq"), ("kvq_gumbel_", "vq"), ("kvq_fp8_", "fp8_quantize"), ("kvq_reduce_batch", "reduce"),
              ("kvq_colsum", "reduce"), ("kvq_sum_slabs", "reduce"), ("kvq_gelu_", "gelu"), ("kvq_embed_grad", "embedding_grad"),
              ("kvq_zero_ranges", "embedding_grad"))
 _fam = None          # None = off; else dict(events=[(family, e0, e1)], cal=[(e0, e1)])

@@ -24,6 +24,7 @@ losses and every parameter gradient against the autograd path (kvq.bert + torch 
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict, List, Tuple
 
@@ -172,7 +173,7 @@ class FlatParams:
         # engine_of(model)) never touches them -- 2.5 of the 4.5 GB of flat buffers at bert-base.  The first training steps run
         # eagerly, so the allocation never falls inside a hipGraph capture.
         self._device, self._amsgrad = device, amsgrad
-        self._grad = self._m = self._v = self._vmax = self._acc = None
+        self._grad = self._m = self._v = self._vmax = self._acc = self._ema = None
         # contiguous trainable ranges (Adam is launched once per range; one range in `full` mode)
         self.ranges: List[Tuple[int, int]] = []
         for name, p, padded in entries:
@@ -224,6 +225,12 @@ class FlatParams:
     def acc(self):
         """f32 sum / mean of the micro-batch gradients (TrainEngine(grad_accum > 1) only: nothing else touches it)."""
         return self._lazy("_acc", torch.float32)
+
+    @property
+    def ema(self):
+        """f32 moving average of the master buffer over the trainable ranges (TrainEngine(weight_ema=...) only: nothing else touches
+        it; a frozen element is never written and never read)."""
+        return self._lazy("_ema", torch.float32)
 
     def optimizer_state_allocated(self) -> bool:
         return self._grad is not None or self._m is not None or self._v is not None
@@ -315,6 +322,8 @@ class _StepGraphs:
                         self.out.update(eng._guard_out)
                     if eng.revive_after is not None and final:
                         self.out["codes_revived"] = eng._rv_counter[0]
+                    if eng.weight_ema is not None and final:
+                        self.out["weight_ema_decay"] = eng._wema_out
                     ok = True
                 finally:
                     eng._cap = None
@@ -394,10 +403,12 @@ class _StepGraphs:
 class TrainEngine:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
                  milestones=None, gamma=0.1, loss_recon_scale=1.0, loss_vq_scale=1.0, seed=1234,
-                 bucket_mib=64, process_group=None, fp8_forward=None, fp8_backward=None, max_grad_norm=None, grad_accum=None):
+                 bucket_mib=64, process_group=None, fp8_forward=None, fp8_backward=None, max_grad_norm=None, grad_accum=None,
+                 weight_ema=None):
         self.model = model
         self.grad_accum = self.check_grad_accum(grad_accum, env=True)
         self.max_grad_norm = self.check_max_grad_norm(max_grad_norm, env=True)     # (before anything is laid out: a bad value changes nothing)
+        self.weight_ema = self.check_weight_ema(weight_ema, env=True)
         # option, off by default: codebook revival.  The quantiser's revive_after; None there: KVQ_VQ_REVIVE_AFTER
         # from the environment, as max_grad_norm reads KVQ_MAX_GRAD_NORM (unset / empty: off).  A model without a quantiser ignores it.
         self.revive_after = None
@@ -600,6 +611,9 @@ class TrainEngine:
         if fp8_forward not in (False, "fused", "wide", "all"):
             raise KvqError(f"TrainEngine: fp8_forward must be False, True / \"fused\", \"wide\" or \"all\", got {fp8_forward!r}")
         self.fp8 = bool(fp8_forward)
+        if self.fp8 and self.weight_ema is not None:
+            raise KvqError("TrainEngine: weight_ema with fp8 forward GEMMs (fp8_forward / KVQ_FP8): evaluation under the average swaps "
+                           "the weights, and their fp8 mirror would have to be re-quantised in the middle of a scale period")
         self._fp8_fused = fp8_forward == "fused"
         self._fp8_all = fp8_forward in ("all", "fused")
         self._x8 = {}                      # data_ptr of a bf16 activation -> its fp8 copy, left by the producer for ONE fp8 GEMM
@@ -641,6 +655,19 @@ class TrainEngine:
             for a in self.aux:
                 if a["p"].requires_grad:
                     a["acc"] = torch.zeros_like(a["p"].data)
+        # option, off by default: an exponential moving average of the trained weights.  weight_ema = decay
+        # in (0, 1): behind Adam every optimiser step moves an f32 average of each trainable range of the master buffer and of each
+        # aux parameter Adam owns (kvq_weight_ema_update; the first update stores, the decay warms up as min(decay, (1 + t) / (10 + t))),
+        # and weight_ema_applied() evaluates under it.  None: KVQ_WEIGHT_EMA from the environment, as max_grad_norm reads
+        # KVQ_MAX_GRAD_NORM (unset / empty: off).  Off = no buffer, no launch added, today's step and graphs.  The update count lives
+        # on the device (include/kvq.h "exponential moving average of the trained weights"): a skipped step does not count.
+        self._wema_state, self._wema_applied = None, False
+        if self.weight_ema is not None:
+            self._wema_state = nnops.new_weight_ema_state(dev)
+            self._wema_out = self._wema_state[1:2].view(torch.float32)[0]      # last_decay, a view: train_step hands out copies
+            for a in self.aux:
+                if a["p"].requires_grad:
+                    a["ema"] = torch.zeros_like(a["p"].data)
         # fp8 input-gradient GEMMs of the last training step and their weight keys in launch order: counted while the step is
         # scheduled (eagerly, or at capture -- a replay restores the counts of the graphs it replays)
         self.fp8_bwd_launches = 0
@@ -1438,6 +1465,8 @@ class TrainEngine:
         latents [B, Se, H] replaces the encoder's output (input_ids / attention_mask are not read and may be None),
         stop_after_encoder returns before the quantiser, skip_quantizer hands the encoder output (or `latents`) to the decoder as it
         is, want_latents adds z / z_q to what stop_after_quantizer returns."""
+        if compute_grads:
+            self._wema_refuse("forward_backward(compute_grads=True)")
         self._stop_after_quantizer = bool(stop_after_quantizer) and not compute_grads
         if (latents is not None or stop_after_encoder or skip_quantizer or want_latents) and (compute_grads or defer_backward):
             raise KvqError("TrainEngine: latents / stop_after_encoder / skip_quantizer / want_latents are forward-only arguments")
@@ -2170,6 +2199,83 @@ class TrainEngine:
             raise KvqError(f"TrainEngine: grad_accum must be None or an integer >= 1, got {v!r}")
         return v
 
+    @staticmethod
+    def check_weight_ema(v, env=False):
+        """None (off), or the float in (0, 1) a TrainEngine(weight_ema=...) accepts; anything else raises KvqError.
+        env: None means KVQ_WEIGHT_EMA from the environment (unset or empty: off)."""
+        if v is None and env and os.environ.get("KVQ_WEIGHT_EMA", "") != "":
+            try:
+                v = float(os.environ["KVQ_WEIGHT_EMA"])
+            except ValueError:
+                raise KvqError(f"TrainEngine: KVQ_WEIGHT_EMA (weight_ema) must be a float in (0, 1), got "
+                               f"{os.environ['KVQ_WEIGHT_EMA']!r}") from None
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 < v < 1:
+            raise KvqError(f"TrainEngine: weight_ema must be None or a float in (0, 1), got {v!r}")
+        return float(v)
+
+    @property
+    def weight_ema_updates(self):
+        """Updates the average has taken so far (weight_ema only, 0 otherwise; synchronises).  A skipped step applies none."""
+        return nnops.read_weight_ema_state(self._wema_state)[0] if self._wema_state is not None else 0
+
+    def _wema_pairs(self):
+        """(parameters, average, bf16 shadow | None) of everything that is averaged: the trainable ranges of the flat buffer, then
+        the aux parameters Adam owns.  Views of fixed storage: what a captured launch or a swap addresses never moves."""
+        fl = self.flat
+        for (a, b) in fl.ranges:
+            yield fl.master[a:b], fl.ema[a:b], (fl.shadow[a:b] if fl.shadow is not fl.master else None)
+        for x in self.aux:
+            if x["p"].requires_grad:
+                yield x["p"].data.view(-1), x["ema"].view(-1), None
+
+    def _weight_ema_update(self):
+        """weight_ema, behind the step's last write to a parameter (Adam, the revived codebook rows): one update launch per range and
+        per aux parameter, then the count moves.  Gated by the gradient guard like the Adam launches in front of it."""
+        if self.weight_ema is None:
+            return
+        for p, ema, _ in self._wema_pairs():
+            nnops.weight_ema_update(p, ema, self._wema_state, self.weight_ema, guard=self._guard)
+        nnops.weight_ema_advance(self._wema_state, self.weight_ema, guard=self._guard)
+
+    def _wema_refuse(self, what):
+        if self._wema_applied:
+            raise KvqError(f"TrainEngine.{what}: called inside weight_ema_applied() -- the parameters hold the average, the master "
+                           f"weights sit in the average's buffer; leave the scope first")
+
+    def _wema_swap(self):
+        with torch.no_grad():
+            for p, ema, shadow in self._wema_pairs():
+                nnops.weight_ema_swap(p, ema, shadow=shadow)
+        if getattr(self, "_epack", None) is not None:
+            self._E_version = None             # the codebook changed under its pack: the next quantiser call repacks it
+
+    @contextlib.contextmanager
+    def weight_ema_applied(self):
+        """Evaluate under the average: on entry every averaged range and aux parameter changes places with its average
+        (kvq_weight_ema_swap, which also writes the bf16 shadow), on exit they change back -- exactly, bit for bit.  No address moves
+        (captured steps stay valid) and no tensor version is bumped.  Inside, model.state_dict(), eval_step, forward_logits, encode /
+        decode and attention_maps see the averaged weights; whatever would train on them, or save / load the engine's state, raises.
+        Before the first update there is nothing to apply: nothing is swapped (the scope still refuses what it refuses)."""
+        if self.weight_ema is None:
+            raise KvqError("TrainEngine.weight_ema_applied: the engine keeps no average (weight_ema / KVQ_WEIGHT_EMA is off)")
+        self._wema_refuse("weight_ema_applied")
+        if self._cap is not None or self._in_fb:
+            raise KvqError("TrainEngine.weight_ema_applied: called inside a step")
+        swap = self.weight_ema_updates > 0
+        self._wema_applied = True
+        try:
+            if swap:
+                self._wema_swap()
+            yield self
+        finally:
+            try:
+                if swap:
+                    self._wema_swap()
+            finally:
+                self._wema_applied = False
+
     @property
     def skipped_steps(self):
         """Optimiser steps skipped so far because their gradient was not finite (max_grad_norm only; synchronises)."""
@@ -2263,6 +2369,7 @@ class TrainEngine:
                                     shadow=fl.shadow[a:b] if fl.shadow is not fl.master else None, guard=self._guard)
 
     def optimizer_step(self):
+        self._wema_refuse("optimizer_step")
         fl = self.flat
         b1, b2 = self.betas
         cut = 0
@@ -2288,6 +2395,7 @@ class TrainEngine:
             self._adam_ranges(0, fl.n)
             self._adam_aux()
             self._revive_apply()
+            self._weight_ema_update()
             self._after_update()
             return
         # step += 1, lr after the milestones, bias corrections: computed on the device, read there by the Adam kernels
@@ -2298,6 +2406,7 @@ class TrainEngine:
             self._adam_ranges(0, cut)
         self._adam_aux()
         self._revive_apply()
+        self._weight_ema_update()
         self._after_update()
 
     def _adam_aux(self):
@@ -2362,6 +2471,7 @@ class TrainEngine:
             "w8_period": int(self._w8_period) if self.fp8 else None, "w8_in_adam": bool(self._w8_in_adam) if self.fp8 else None,
             "w8_keys": list(self._w8_index) if self.fp8 else [],
             "world": int(self.world),
+            **({"weight_ema": float(self.weight_ema)} if self.weight_ema is not None else {}),     # off: exactly the keys of before
         }
 
     def _state_slots(self, present) -> dict:
@@ -2376,8 +2486,12 @@ class TrainEngine:
         pending = self.grad_accum > 1 and present("host.accum_pending")
         if self.grad_accum > 1:
             slots["flat.acc"] = (lambda: fl.acc, f32, fl.n, pending)
+        if self.weight_ema is not None:           # (absent in a state from before the first update, like the moments)
+            slots["flat.ema"] = (lambda: fl.ema, f32, fl.n, present("flat.ema"))
+            slots["structs.weight_ema"] = (lambda: self._wema_state, i64, 2, True)
         for i, a in enumerate(self.aux):
-            for k in ("p", "m", "v") + (("vmax",) if a["vmax"] is not None else ()) + (("acc",) if "acc" in a else ()):
+            for k in ("p", "m", "v") + (("vmax",) if a["vmax"] is not None else ()) + (("acc",) if "acc" in a else ()) \
+                    + (("ema",) if "ema" in a else ()):
                 get = (lambda a=a: a["p"].data) if k == "p" else (lambda a=a, k=k: a[k])
                 slots[f"aux.{i}.{k}"] = (get, a["p"].dtype, a["p"].numel(), pending if k == "acc" else True)
         slots["structs.state"] = (lambda: self._state, i64, 3, True)
@@ -2411,6 +2525,7 @@ class TrainEngine:
         device structs travel as raw words, so a state is tied to their layout in include/kvq.h (kvq_version).  flat.grad and
         flat.shadow are not state (every backward rewrites the first, refresh_shadow() rebuilds the second), nor are the graphs."""
         fl = self.flat
+        self._wema_refuse("state_dict")
         if self._cap is not None or self._in_fb:
             raise KvqError("TrainEngine.state_dict: called inside a step")
         pending = self._accum_host > 0
@@ -2420,6 +2535,8 @@ class TrainEngine:
                 flat[k] = getattr(fl, "_" + k)
         if pending:
             flat["acc"] = fl.acc
+        if fl._ema is not None:
+            flat["ema"] = fl._ema
         aux = []
         for a in self.aux:
             d = {"p": a["p"].data, "m": a["m"], "v": a["v"]}
@@ -2427,12 +2544,16 @@ class TrainEngine:
                 d["vmax"] = a["vmax"]
             if pending and "acc" in a:
                 d["acc"] = a["acc"]
+            if "ema" in a:
+                d["ema"] = a["ema"]
             aux.append(d)
         structs = {"state": self._state}
         if self._acc_state is not None:
             structs["acc_state"] = self._acc_state
         if self._guard is not None:
             structs["guard"] = self._guard
+        if self._wema_state is not None:
+            structs["weight_ema"] = self._wema_state
         if self.revive_after is not None:
             structs["revive_idle"], structs["revive_counter"] = self._rv_idle, self._rv_counter
         if self.vq_kind in ("VectorQuantizer", "MultiVectorQuantizer") and not self.E.requires_grad:
@@ -2473,6 +2594,7 @@ class TrainEngine:
         load has written nothing.  Then copies INTO the existing buffers: no attribute a captured graph may hold the address of is
         rebound, an engine that replays graphs keeps replaying them.  Not sync_from_model(): that would re-quantise the fp8 weights
         with fresh scales in the middle of a scale period."""
+        self._wema_refuse("load_state_dict")
         if self._cap is not None or self._in_fb:
             raise KvqError("TrainEngine.load_state_dict: called inside a step")
         if not isinstance(state, dict):
@@ -2656,6 +2778,8 @@ class TrainEngine:
             out.update({k: v.clone() for k, v in self._guard_out.items()})
         if self.revive_after is not None and final:      # counter.last (its upper word is padding: 0), rewritten by the next step
             out["codes_revived"] = self._rv_counter[0].clone()
+        if self.weight_ema is not None and final:
+            out["weight_ema_decay"] = self._wema_out.clone()
         out["optimizer_step"] = final
         return out
 
@@ -2673,6 +2797,7 @@ class TrainEngine:
         """What train_step runs behind forward_backward(compute_grads=True), for callers that schedule the two halves themselves:
         the optimiser -- or, with grad_accum > 1, this micro-step's accumulation and the optimiser on the last one of a cycle.
         Returns whether the optimiser ran."""
+        self._wema_refuse("finish_step")
         final = self._accum_final()
         self._finish_step(final)
         self._accum_note(final)
@@ -2687,6 +2812,7 @@ class TrainEngine:
         _normalise_prepared().  Once a batch shape has been seen twice the step is replayed from a chain of hipGraphs
         (_StepGraphs: the quantiser and, on multi-GPU runs, the RCCL all-reduces stay eager launches between the graphs); the
         host then issues a handful of launches per step instead of ~800.  KVQ_GRAPH=0 keeps every launch eager."""
+        self._wema_refuse("train_step")
         if dec_ids is None and (dec_mask is not None or target_ids is not None):
             if target_ids is None:
                 raise KvqError("TrainEngine.train_step: dec_mask without dec_ids")

@@ -460,6 +460,59 @@ def accum_advance(state, A):
     check(lib().kvq_accum_advance(_accum_ptr(state), int(A), stream_ptr()), "kvq_accum_advance")
 
 
+# ---- EMA of the trained weights (include/kvq.h "exponential moving average of the trained weights") -------------------------------
+def new_weight_ema_state(device):
+    """16 zeroed bytes: struct { uint64 updates; float last_decay; uint32 pad; } of include/kvq.h."""
+    return torch.zeros(2, dtype=torch.int64, device=device)
+
+
+def _wema_ptr(state):
+    if not torch.is_tensor(state) or state.dtype != torch.int64 or state.numel() != 2 or not state.is_contiguous():
+        raise KvqError("a weight-EMA state is new_weight_ema_state()'s tensor (2 x int64)")
+    require_gpu(state)
+    return state.data_ptr()
+
+
+def read_weight_ema_state(state):
+    """(updates, last_decay) -- synchronises; for tests, logging and TrainEngine.weight_ema_updates."""
+    _wema_ptr(state)
+    raw = state.cpu()
+    return int(raw[0]), float(raw[1:2].view(torch.float32)[0])
+
+
+def _wema_pair(what, p, ema):
+    require_gpu(p, ema)
+    if p.dtype != torch.float32 or not p.is_contiguous() or p.numel() < 1:
+        raise KvqError(f"{what}: contiguous float32 parameters of at least one element required")
+    if ema.dtype != torch.float32 or not ema.is_contiguous() or ema.numel() != p.numel():
+        raise KvqError(f"{what}: the average is a contiguous float32 tensor of the parameters' length")
+
+
+def weight_ema_update(p, ema, state, decay, guard=None):
+    """ema (f32, as long as p) = p on the first update, d * ema + (1 - d) * p in f64 on the others, d = min(decay, (1 + t) / (10 + t))
+    with the update count t read on the device from `state` (new_weight_ema_state).  guard: a gradient guard state -- nothing is
+    stored when guard.skip is set."""
+    _wema_pair("weight_ema_update", p, ema)
+    check(lib().kvq_weight_ema_update(p.data_ptr(), ema.data_ptr(), p.numel(), float(decay), _wema_ptr(state),
+                                      _guard_ptr(guard) if guard is not None else None, stream_ptr()), "kvq_weight_ema_update")
+
+
+def weight_ema_advance(state, decay, guard=None):
+    """last_decay = the d of this step's updates (0 for the storing one), updates += 1, on the device; nothing when guard.skip is set."""
+    check(lib().kvq_weight_ema_advance(_wema_ptr(state), float(decay), _guard_ptr(guard) if guard is not None else None, stream_ptr()),
+          "kvq_weight_ema_advance")
+
+
+def weight_ema_swap(p, ema, shadow=None):
+    """p <-> ema, exactly; shadow (bf16, as long as p): the bf16 copy of the new p, rounded as the Adam kernel rounds its shadow."""
+    _wema_pair("weight_ema_swap", p, ema)
+    if shadow is not None:
+        require_gpu(shadow)
+        if shadow.dtype != torch.bfloat16 or not shadow.is_contiguous() or shadow.numel() != p.numel():
+            raise KvqError("weight_ema_swap: the shadow is a contiguous bfloat16 tensor of the parameters' length")
+    check(lib().kvq_weight_ema_swap(p.data_ptr(), ema.data_ptr(), _p(shadow), p.numel(), stream_ptr()), "kvq_weight_ema_swap")
+
+
 def set_seed_offset(step_state):
     """Dropout-bearing kernels launched from now on use seed + step_state.step (read on the device); None switches it off.  (Any
     device tensor whose first word is a uint64 count will do: an accumulating engine passes its accumulation state.)"""

@@ -106,3 +106,22 @@ def revive_epoch_record(engine, stats_stage_run: dict, stage: str = "train"):
     if engine is None or getattr(engine, "revive_after", None) is None or total is None:
         return None
     return {f"{stage}/codes_revived": int(total), f"{stage}/codes_revived_total": int(engine.revived_codes)}
+
+
+# ---- TrainEngine(weight_ema=...): evaluation under the moving average of the weights, in the trainers ------------------------------
+def weight_ema_scope(engine, enabled: bool = True):
+    """The context a validation / test stage runs in: engine.weight_ema_applied() when the engine keeps an average and `enabled`
+    (WEIGHT_EMA_EVAL) says to evaluate under it, a null context otherwise (no engine, option off, switched off)."""
+    import contextlib
+    if engine is None or getattr(engine, "weight_ema", None) is None or not enabled:
+        return contextlib.nullcontext()
+    return engine.weight_ema_applied()
+
+
+def weight_ema_epoch_record(engine, last_decay=None, stage: str = "train"):
+    """End of a training stage, after its statistics were read: {"<stage>/weight_ema_decay": the decay of the stage's last applied
+    update (None before the first), "<stage>/weight_ema_updates": updates so far} | None with the option off."""
+    if engine is None or getattr(engine, "weight_ema", None) is None:
+        return None
+    return {f"{stage}/weight_ema_decay": float(last_decay) if last_decay is not None else None,
+            f"{stage}/weight_ema_updates": int(engine.weight_ema_updates)}

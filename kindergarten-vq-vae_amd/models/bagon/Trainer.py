@@ -29,7 +29,8 @@ from torch import Tensor, no_grad, save
 
 from common.consts import *  # noqa: F401,F403
 from common.tensor_utils import replace_pct_rand_values
-from kvq.runlog import drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note, optimizer_steps_epoch
+from kvq.runlog import (drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note, optimizer_steps_epoch,
+                        weight_ema_epoch_record, weight_ema_scope)
 from kvq.train_state import check_every, restore_trainer, save_train_state, trainer_state
 
 
@@ -96,6 +97,8 @@ def step(device, model, tokenizer_encoder, tokenizer_decoder,
         stats["grad_norm_step"] = out["grad_norm"]
     if engine is not None and "optimizer_step" in out:    # grad_accum: whether this call ran the optimiser (a Python bool, no device read)
         stats["optimizer_step"] = out["optimizer_step"]
+    if engine is not None and "weight_ema_decay" in out:  # weight_ema: the decay this step's update used, a device scalar like the others
+        stats["weight_ema_decay_step"] = out["weight_ema_decay"]
     return stats, input_ids_encoder, input_ids_decoder, recon_ids, labels
 
 
@@ -106,6 +109,8 @@ def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batc
     stats_stage_run["padding_tokens_pct_run"] += stats_step["padding_tokens_pct_step"]
     grad_norm_note(stats_stage_run, stats_step)
     optimizer_step_note(stats_stage_run, stats_step)
+    if "weight_ema_decay_step" in stats_step:     # the last one of the stage is what the epoch's line reports
+        stats_stage_run["weight_ema_decay_last"] = stats_step["weight_ema_decay_step"]
     return stats_stage_run
 
 
@@ -247,8 +252,10 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
           encoder_perturb_train_pct, encoder_perturb_val_pct, decoder_perturb_train_pct, decoder_perturb_val_pct,
           n_epochs_to_decode_after, decoded_sentences, opt, lr_sched, n_epochs, vocab_size_encoder, vocab_size_decoder,
           wandb_run, run_path, export_checkpoint=True, grad_sync=None, engine=None, is_main=True,
-          train_state_path=None, train_state_every: int = 1, resume=None, train_state_config=None):
-    """train_state_path: the run's training-state file (kvq.train_state; None: none is written), rewritten at the end of every
+          train_state_path=None, train_state_every: int = 1, resume=None, train_state_config=None, weight_ema_eval: bool = True):
+    """weight_ema_eval: with an engine that keeps an average of the weights (TrainEngine(weight_ema=...)), run every validation
+    stage under it and write the best-val checkpoints while it is applied: they hold the weights that were scored.
+    train_state_path: the run's training-state file (kvq.train_state; None: none is written), rewritten at the end of every
     train_state_every-th epoch and of the last one, behind validation and the best checkpoints.  resume: such a file's dict
     (load_train_state) -- the loop starts behind its last finished epoch; model and engine / optimiser were loaded by the caller.
     train_state_config: the run's configuration, stored in the file."""
@@ -285,6 +292,12 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
             if console is not None:
                 console.print(f"    | grad_norm: {guard_rec['train/grad_norm']:.6f} | skipped steps: {guard_rec['train/skipped_steps']}")
         n_opt = optimizer_steps_epoch(run, s)                                             # grad_accum: a cycle left open carries into the next epoch
+        wema_rec = weight_ema_epoch_record(engine, run.pop("weight_ema_decay_last", None))      # weight_ema: decay in force, updates so far
+        if wema_rec is not None:
+            wandb_run.log({"epoch": epoch, **wema_rec})
+            if console is not None:
+                console.print(f"    | weight EMA decay: {wema_rec['train/weight_ema_decay']} | updates: {wema_rec['train/weight_ema_updates']}"
+                              f"{'' if weight_ema_eval else ' | evaluation on the live weights'}")
         # sentences/s of THIS rank's train stage, loop and all (end_of_epoch_stats_update has just turned the device sums into
         # floats: the stage's kernels have finished).  An extra log entry, not one of the reference's keys.
         wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": s, "perf/optimizer_steps": n_opt,
@@ -294,13 +307,14 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
         if export_checkpoint and is_main:
             checkpoint(stats_train_best, model, run_path, "train")
         model.eval()
-        run, n, s = _stage("val", dl_val, n_batches_val, step_kw, None, None, (encoder_perturb_val_pct, decoder_perturb_val_pct),
-                           dec, epoch, None, engine, prg, tasks and tasks[1])
-        stats_val_run, stats_val_best = end_of_epoch_stats_update(run, stats_val_best, n, s)
-        end_of_epoch_print(stats_val_run, stats_val_best, console, epoch, False, COLOR_VAL, STATS_EMOJI_VAL, epoch != n_epochs)
-        wandb_run.log(create_wandb_log_dict(epoch, stats_val_run, "val"))
-        if export_checkpoint and is_main:
-            checkpoint(stats_val_best, model, run_path, "val")
+        with weight_ema_scope(engine, weight_ema_eval):       # weight_ema: validation and the best-val checkpoints under the average
+            run, n, s = _stage("val", dl_val, n_batches_val, step_kw, None, None, (encoder_perturb_val_pct, decoder_perturb_val_pct),
+                               dec, epoch, None, engine, prg, tasks and tasks[1])
+            stats_val_run, stats_val_best = end_of_epoch_stats_update(run, stats_val_best, n, s)
+            end_of_epoch_print(stats_val_run, stats_val_best, console, epoch, False, COLOR_VAL, STATS_EMOJI_VAL, epoch != n_epochs)
+            wandb_run.log(create_wandb_log_dict(epoch, stats_val_run, "val"))
+            if export_checkpoint and is_main:
+                checkpoint(stats_val_best, model, run_path, "val")
         hist.append((stats_train_run, stats_val_run))
         if train_state_path is not None and (epoch % train_state_every == 0 or epoch == n_epochs):
             # (before drop_open_accumulation: a cycle the last epoch left open travels in the file and continues in a resumed run)
@@ -317,7 +331,9 @@ def test(prg, console, device, dl_test, n_batches_test, model, tokenizer_encoder
          tokenizer_encoder_add_special_tokens, tokenized_encoder_sentence_max_length,
          tokenizer_decoder_add_special_tokens, tokenized_decoder_sentence_max_length,
          encoder_perturb_test_pct, decoder_perturb_test_pct, decoded_sentences, vocab_size_encoder, vocab_size_decoder, epoch,
-         wandb_run, engine=None):
+         wandb_run, engine=None, weight_ema_eval: bool = True):
+    """weight_ema_eval: with an engine that keeps an average of the weights, score the test split under it (False: under the
+    weights the model holds -- what a caller passes who has just loaded a checkpoint that already holds the average)."""
     step_kw = dict(device=device, model=model, tokenizer_encoder=tokenizer_encoder, tokenizer_decoder=tokenizer_decoder,
                    tokenizer_encoder_add_special_tokens=tokenizer_encoder_add_special_tokens,
                    tokenized_encoder_sentence_max_length=tokenized_encoder_sentence_max_length,
@@ -325,8 +341,9 @@ def test(prg, console, device, dl_test, n_batches_test, model, tokenizer_encoder
                    tokenized_decoder_sentence_max_length=tokenized_decoder_sentence_max_length,
                    vocab_size_encoder=vocab_size_encoder, vocab_size_decoder=vocab_size_decoder, console=console)
     model.eval()
-    run, n, s = _stage("test", dl_test, n_batches_test, step_kw, None, None, (encoder_perturb_test_pct, decoder_perturb_test_pct),
-                       decoded_sentences, epoch, None, engine)
+    with weight_ema_scope(engine, weight_ema_eval):
+        run, n, s = _stage("test", dl_test, n_batches_test, step_kw, None, None, (encoder_perturb_test_pct, decoder_perturb_test_pct),
+                           decoded_sentences, epoch, None, engine)
     stats_test_run, stats_test_best = end_of_epoch_stats_update(run, init_stats_best(), n, s)
     end_of_epoch_print(stats_test_run, stats_test_best, console, epoch, False, COLOR_TEST, STATS_EMOJI_TEST, True)
     wandb_run.log(create_wandb_log_dict(epoch, stats_test_run, "test"))

@@ -52,6 +52,8 @@ FP8_FORWARD = False             # extension (BASELINE.json configs[4]): forward 
 FP8_BACKWARD = False            # option on top of FP8_FORWARD: input-gradient GEMMs on fp8 (e5m2 gradients, transposed e4m3 weights); DESIGN.md section 5
 MAX_GRAD_NORM = None            # None (off) | float > 0 | float("inf"): the engine step clips its gradient by the global norm and skips non-finite steps (inf: measure and skip only); KVQ_MAX_GRAD_NORM; DESIGN.md section 5b
 GRAD_ACCUM_STEPS = 1            # int >= 1: train_step calls (micro-batches) per optimiser step -- the engine sums their gradients in f32 and Adam reads the mean; MILESTONES, engine.step_count and the bias corrections count OPTIMISER steps, perf/train_steps counts calls; KVQ_GRAD_ACCUM; DESIGN.md section 5d
+WEIGHT_EMA_DECAY = None       # None (off) | float in (0, 1): the engine keeps an f32 moving average of the trained weights, updated behind Adam inside the step (the decay warms up as min(decay, (1 + t) / (10 + t))); KVQ_WEIGHT_EMA; DESIGN.md section 5f
+WEIGHT_EMA_EVAL = True         # with WEIGHT_EMA_DECAY: validation, the best-val checkpoints and the test stage run under the average (False: the average is kept and saved with the training state, evaluation reads the live weights)
 
 RUNS_DIR = "./runs/Bagon"
 EXPORT_CHECKPOINT = True
@@ -85,6 +87,19 @@ if isinstance(GRAD_ACCUM_STEPS, str) and not GRAD_ACCUM_STEPS.strip():
     GRAD_ACCUM_STEPS = 1
 if isinstance(GRAD_ACCUM_STEPS, bool) or not isinstance(GRAD_ACCUM_STEPS, int) or GRAD_ACCUM_STEPS < 1:
     raise ValueError(f"GRAD_ACCUM_STEPS (KVQ_GRAD_ACCUM) must be an integer >= 1, got {GRAD_ACCUM_STEPS!r}")
+_v = _os.environ.get("KVQ_WEIGHT_EMA", "").strip()      # the variable TrainEngine itself reads; it wins over KVQ_WEIGHT_EMA_DECAY; empty = unset
+if _v:
+    try:
+        WEIGHT_EMA_DECAY = _ast.literal_eval(_v)
+    except (ValueError, SyntaxError):
+        WEIGHT_EMA_DECAY = _v
+if isinstance(WEIGHT_EMA_DECAY, str) and not WEIGHT_EMA_DECAY.strip():
+    WEIGHT_EMA_DECAY = None
+if WEIGHT_EMA_DECAY is not None and (isinstance(WEIGHT_EMA_DECAY, bool) or not isinstance(WEIGHT_EMA_DECAY, (int, float))
+                                     or not 0 < WEIGHT_EMA_DECAY < 1):
+    raise ValueError(f"WEIGHT_EMA_DECAY (KVQ_WEIGHT_EMA) must be None or a float in (0, 1), got {WEIGHT_EMA_DECAY!r}")
+if not isinstance(WEIGHT_EMA_EVAL, bool):
+    raise ValueError(f"WEIGHT_EMA_EVAL (KVQ_WEIGHT_EMA_EVAL) must be True or False, got {WEIGHT_EMA_EVAL!r}")
 if isinstance(TRAIN_STATE_EVERY_EPOCHS, bool) or not isinstance(TRAIN_STATE_EVERY_EPOCHS, int) or TRAIN_STATE_EVERY_EPOCHS < 1:
     raise ValueError(f"TRAIN_STATE_EVERY_EPOCHS (KVQ_TRAIN_STATE_EVERY_EPOCHS) must be an integer >= 1, got {TRAIN_STATE_EVERY_EPOCHS!r}")
 if isinstance(RESUME_FROM, str) and not RESUME_FROM.strip():      # KVQ_RESUME_FROM= (empty) = unset

@@ -95,7 +95,8 @@ def main():
                              fp8_forward=FP8_FORWARD if FP8_FORWARD else None,       # (None: the KVQ_FP8 environment switch decides)
                              fp8_backward=FP8_BACKWARD if FP8_BACKWARD else None,     # (None: KVQ_FP8_BACKWARD)
                              max_grad_norm=MAX_GRAD_NORM,                             # (None: off, or KVQ_MAX_GRAD_NORM)
-                             grad_accum=GRAD_ACCUM_STEPS)                             # (1: off; the configuration has read KVQ_GRAD_ACCUM)
+                             grad_accum=GRAD_ACCUM_STEPS,                             # (1: off; the configuration has read KVQ_GRAD_ACCUM)
+                             weight_ema=WEIGHT_EMA_DECAY)                             # (None: off; the configuration has read KVQ_WEIGHT_EMA)
         if TOKEN_CACHE and same_tok:
             for c in caches:
                 c.packed_pad_id = engine.pad_idx if not any_perturb else "off"     # perturbed ids are sorted by the engine itself
@@ -103,6 +104,8 @@ def main():
         grad_sync = ddp.GradSync(model.parameters(), bucket_mib=GRAD_BUCKET_MIB)
     if engine is None and GRAD_ACCUM_STEPS > 1:      # the autograd path steps its optimiser per batch: no silent batch of another size
         raise SystemExit("GRAD_ACCUM_STEPS > 1 (KVQ_GRAD_ACCUM) needs the engine (USE_ENGINE and a model shape it supports)")
+    if engine is None and WEIGHT_EMA_DECAY is not None:      # the average is built inside the engine's step: no silent run without it
+        raise SystemExit("WEIGHT_EMA_DECAY (KVQ_WEIGHT_EMA) needs the engine (USE_ENGINE and a model shape it supports)")
 
     # RESUME_FROM: continue a run from its training-state file (kvq/train_state.py).  Every rank reads the SAME
     # file and takes the same decisions from it, so a refusal stops all of them; a rank that cannot read it stops all of them too.
@@ -141,7 +144,8 @@ def main():
     run_conf = get_config()
     run_conf.update({"n_params": model.model_params_summary_dict(), "optimizer": str(opt), "run_id": run_id, "world_size": world,
                      "grad_accum": engine.grad_accum if engine is not None else 1,
-                     "max_grad_norm": engine.max_grad_norm if engine is not None else None})     # what the step really runs with
+                     "max_grad_norm": engine.max_grad_norm if engine is not None else None,      # what the step really runs with
+                     "weight_ema": engine.weight_ema if engine is not None else None})
     if is_main:
         os.makedirs(run_path, exist_ok=True)
         if resume is None:                    # (a resumed run leaves the stored run's run_conf.json as it is)
@@ -166,7 +170,8 @@ def main():
           decoder_perturb_train_pct=DECODER_PERTURB_TRAIN_PCT, decoder_perturb_val_pct=DECODER_PERTURB_VAL_PCT, wandb_run=wandb_run,
           run_path=run_path, export_checkpoint=EXPORT_CHECKPOINT, grad_sync=grad_sync, engine=engine, is_main=is_main,
           train_state_path=f"{run_path}/bagon_train_state_last.pth" if EXPORT_TRAIN_STATE else None,
-          train_state_every=TRAIN_STATE_EVERY_EPOCHS, resume=resume, train_state_config=state_config, **common)
+          train_state_every=TRAIN_STATE_EVERY_EPOCHS, resume=resume, train_state_config=state_config,
+          weight_ema_eval=WEIGHT_EMA_EVAL, **common)
     # The test stage runs on EVERY rank (each on its shard of the test split): test() ends in the stage's all-reduce of the
     # statistics (Trainer._sum_over_ranks), a collective every rank has to enter.  Rank 0 wrote the checkpoint; agree() puts a
     # barrier behind that write and hands every rank rank 0's answer to "is there a best checkpoint".
@@ -177,7 +182,10 @@ def main():
             engine.sync_from_model()
         test(prg=None, console=console, device=device, dl_test=dl_test, n_batches_test=int(len(dl_test) * LIM_BATCHES_TEST_PCT),
              model=model, encoder_perturb_test_pct=ENCODER_PERTURB_TEST_PCT, decoder_perturb_test_pct=DECODER_PERTURB_TEST_PCT,
-             decoded_sentences=decoded, epoch=N_EPOCHS, wandb_run=wandb_run, engine=engine, **common)
+             decoded_sentences=decoded, epoch=N_EPOCHS, wandb_run=wandb_run, engine=engine,
+             # weight_ema: with WEIGHT_EMA_EVAL the checkpoint just loaded was written under the average and HOLDS the averaged
+             # weights that were scored -- they are tested as they are (the scope would put the last epoch's average in their place)
+             weight_ema_eval=False, **common)
     decoded = ddp.gather_lists(decoded)            # every rank decoded its own shard: rank 0 writes them all
     if is_main:
         import pandas as pd

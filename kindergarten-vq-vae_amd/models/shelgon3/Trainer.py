@@ -25,7 +25,7 @@ from torch import Tensor, no_grad, save
 
 from common.consts import *  # noqa: F401,F403  (colours / emoji)
 from kvq.runlog import (codes_revived_note, drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note,
-                        optimizer_steps_epoch, revive_epoch_record)
+                        optimizer_steps_epoch, revive_epoch_record, weight_ema_epoch_record, weight_ema_scope)
 from kvq.train_state import check_every, restore_trainer, save_train_state, trainer_state
 
 
@@ -63,6 +63,8 @@ def step(device, model, tokenizer, tokenizer_add_special_tokens: bool, opt,
             stats["codes_revived_step"] = out["codes_revived"]
         if "optimizer_step" in out:               # grad_accum: whether this call ran the optimiser (a Python bool, no device read)
             stats["optimizer_step"] = out["optimizer_step"]
+        if "weight_ema_decay" in out:             # weight_ema: the decay this step's update used, a device scalar like the others
+            stats["weight_ema_decay_step"] = out["weight_ema_decay"]
         return stats, input_ids, out["recon_ids"]
 
     loss_vq_step, metric_perp_step, _indices, loss_recon_step, acc_step, recon_ids = \
@@ -104,6 +106,8 @@ def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batc
     grad_norm_note(stats_stage_run, stats_step)
     codes_revived_note(stats_stage_run, stats_step)
     optimizer_step_note(stats_stage_run, stats_step)
+    if "weight_ema_decay_step" in stats_step:     # the last one of the stage is what the epoch's line reports
+        stats_stage_run["weight_ema_decay_last"] = stats_step["weight_ema_decay_step"]
     return stats_stage_run
 
 
@@ -233,8 +237,11 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
           loss_recon_rescale_factor: float, loss_recon_weight: float, loss_vq_rescale_factor: float, loss_vq_weight: float,
           loss_perp_rescale_factor: float, loss_perp_weight: float, lr_sched, n_epochs: int, vocab_size: int,
           wandb_run, run_path: str, export_checkpoint: bool, max_length: int = 12, grad_sync=None, is_main: bool = True,
-          engine=None, train_state_path=None, train_state_every: int = 1, resume=None, train_state_config=None):
-    """train_state_path: the run's training-state file (kvq.train_state; None: none is written), rewritten at the end of every
+          engine=None, train_state_path=None, train_state_every: int = 1, resume=None, train_state_config=None,
+          weight_ema_eval: bool = True):
+    """weight_ema_eval: with an engine that keeps an average of the weights (TrainEngine(weight_ema=...)), run every validation
+    stage under it and write the best-val checkpoints while it is applied: they hold the weights that were scored.
+    train_state_path: the run's training-state file (kvq.train_state; None: none is written), rewritten at the end of every
     train_state_every-th epoch and of the last one, behind validation and the best checkpoints.  resume: such a file's dict
     (load_train_state) -- the loop starts behind its last finished epoch; model and engine / optimiser were loaded by the caller.
     train_state_config: the run's configuration, stored in the file."""
@@ -279,6 +286,12 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
             wandb_run.log({"epoch": epoch, **revive_rec})
             if console is not None:
                 console.print(f"    | codes revived: {revive_rec['train/codes_revived']} | so far: {revive_rec['train/codes_revived_total']}")
+        wema_rec = weight_ema_epoch_record(engine, run.pop("weight_ema_decay_last", None))      # weight_ema: decay in force, updates so far
+        if wema_rec is not None:
+            wandb_run.log({"epoch": epoch, **wema_rec})
+            if console is not None:
+                console.print(f"    | weight EMA decay: {wema_rec['train/weight_ema_decay']} | updates: {wema_rec['train/weight_ema_updates']}"
+                              f"{'' if weight_ema_eval else ' | evaluation on the live weights'}")
         # sentences/s of THIS rank's train stage, loop and all (end_of_epoch_stats_update has just turned the device sums into
         # floats: the stage's kernels have finished).  An extra log entry, not one of the reference's keys.
         wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": n_steps, "perf/optimizer_steps": n_opt,
@@ -288,14 +301,15 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
 
         model.eval()
         tick = (lambda: (prg.advance(tasks[2], 1), prg.advance(tasks[0], 1 / (n_batches_train + n_batches_val)))) if tasks else None
-        run, n_els, n_steps = _run_stage("val", device, dl_val, n_batches_val, model, tokenizer, tokenizer_add_special_tokens,
-                                         None, None, weights, vocab_size, decode_now, epoch, console, max_length, None, tick,
-                                         engine=engine)
-        stats_val_run, stats_val_best = end_of_epoch_stats_update(run, stats_val_best, n_els, n_steps)
-        end_of_epoch_print(stats_val_run, stats_val_best, console, epoch, False, COLOR_VAL, STATS_EMOJI_VAL, epoch != n_epochs)
-        wandb_run.log(create_wandb_log_dict(epoch, stats_val_run, "val"))
-        if export_checkpoint and is_main:
-            checkpoint(stats_val_best, model, run_path, "val")
+        with weight_ema_scope(engine, weight_ema_eval):       # weight_ema: validation and the best-val checkpoints under the average
+            run, n_els, n_steps = _run_stage("val", device, dl_val, n_batches_val, model, tokenizer, tokenizer_add_special_tokens,
+                                             None, None, weights, vocab_size, decode_now, epoch, console, max_length, None, tick,
+                                             engine=engine)
+            stats_val_run, stats_val_best = end_of_epoch_stats_update(run, stats_val_best, n_els, n_steps)
+            end_of_epoch_print(stats_val_run, stats_val_best, console, epoch, False, COLOR_VAL, STATS_EMOJI_VAL, epoch != n_epochs)
+            wandb_run.log(create_wandb_log_dict(epoch, stats_val_run, "val"))
+            if export_checkpoint and is_main:
+                checkpoint(stats_val_best, model, run_path, "val")
         history.append((dict(stats_train_run), dict(stats_val_run)))
         if train_state_path is not None and (epoch % train_state_every == 0 or epoch == n_epochs):
             # (before drop_open_accumulation: a cycle the last epoch left open travels in the file and continues in a resumed run)
@@ -309,15 +323,18 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
 def test(prg, console, device, dl_test, n_batches_test, model, tokenizer, tokenizer_add_special_tokens: bool,
          loss_recon_rescale_factor: float, loss_recon_weight: float, loss_vq_rescale_factor: float, loss_vq_weight: float,
          loss_perp_rescale_factor: float, loss_perp_weight: float, decoded_sentences: list, vocab_size: int, epoch: int,
-         wandb_run, max_length: int = 12, engine=None):
+         wandb_run, max_length: int = 12, engine=None, weight_ema_eval: bool = True):
+    """weight_ema_eval: with an engine that keeps an average of the weights, score the test split under it (False: under the
+    weights the model holds -- what a caller passes who has just loaded a checkpoint that already holds the average)."""
     weights = dict(loss_recon_rescale_factor=loss_recon_rescale_factor, loss_recon_weight=loss_recon_weight,
                    loss_vq_rescale_factor=loss_vq_rescale_factor, loss_vq_weight=loss_vq_weight,
                    loss_perp_rescale_factor=loss_perp_rescale_factor, loss_perp_weight=loss_perp_weight)
     task = prg.add_task(f"[bold {COLOR_TEST}] Test  batches", total=n_batches_test) if prg is not None else None
     model.eval()
-    run, n_els, n_steps = _run_stage("test", device, dl_test, n_batches_test, model, tokenizer, tokenizer_add_special_tokens,
-                                     None, None, weights, vocab_size, decoded_sentences, epoch, console, max_length, None,
-                                     (lambda: prg.advance(task, 1)) if task is not None else None, engine=engine)
+    with weight_ema_scope(engine, weight_ema_eval):
+        run, n_els, n_steps = _run_stage("test", device, dl_test, n_batches_test, model, tokenizer, tokenizer_add_special_tokens,
+                                         None, None, weights, vocab_size, decoded_sentences, epoch, console, max_length, None,
+                                         (lambda: prg.advance(task, 1)) if task is not None else None, engine=engine)
     stats_test_run, stats_test_best = end_of_epoch_stats_update(run, init_stats_best(), n_els, n_steps)
     end_of_epoch_print(stats_test_run, stats_test_best, console, epoch, False, COLOR_TEST, STATS_EMOJI_TEST, True)
     wandb_run.log(create_wandb_log_dict(epoch, stats_test_run, "test"))

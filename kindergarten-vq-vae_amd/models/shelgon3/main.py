@@ -117,7 +117,8 @@ def main():
                              fp8_forward=FP8_FORWARD if FP8_FORWARD else None,       # (None: the KVQ_FP8 environment switch decides)
                              fp8_backward=FP8_BACKWARD if FP8_BACKWARD else None,     # (None: KVQ_FP8_BACKWARD)
                              max_grad_norm=MAX_GRAD_NORM,                             # (None: off, or KVQ_MAX_GRAD_NORM)
-                             grad_accum=GRAD_ACCUM_STEPS)                             # (1: off; the configuration has read KVQ_GRAD_ACCUM)
+                             grad_accum=GRAD_ACCUM_STEPS,                             # (1: off; the configuration has read KVQ_GRAD_ACCUM)
+                             weight_ema=WEIGHT_EMA_DECAY)                             # (None: off; the configuration has read KVQ_WEIGHT_EMA)
         if TOKEN_CACHE:
             for c in caches:          # the packed sort files the MODEL's padding row under -1 (not the tokenizer's pad id)
                 c.packed_pad_id = engine.pad_idx
@@ -125,6 +126,8 @@ def main():
         grad_sync = ddp.GradSync(model.parameters(), bucket_mib=GRAD_BUCKET_MIB)
     if engine is None and GRAD_ACCUM_STEPS > 1:      # the autograd path steps its optimiser per batch: no silent batch of another size
         raise SystemExit("GRAD_ACCUM_STEPS > 1 (KVQ_GRAD_ACCUM) needs the engine (USE_ENGINE and a model shape it supports)")
+    if engine is None and WEIGHT_EMA_DECAY is not None:      # the average is built inside the engine's step: no silent run without it
+        raise SystemExit("WEIGHT_EMA_DECAY (KVQ_WEIGHT_EMA) needs the engine (USE_ENGINE and a model shape it supports)")
 
     # RESUME_FROM: continue a run from its training-state file (kvq/train_state.py).  Every rank reads the SAME
     # file and takes the same decisions from it, so a refusal stops all of them; a rank that cannot read it stops all of them too.
@@ -168,6 +171,7 @@ def main():
     run_conf.update({"n_params": model.model_params_summary_dict(), "optimizer": str(opt), "run_id": run_id, "world_size": world,
                      "grad_accum": engine.grad_accum if engine is not None else 1,
                      "max_grad_norm": engine.max_grad_norm if engine is not None else None,      # what the step really runs with
+                     "weight_ema": engine.weight_ema if engine is not None else None,
                      "vq_revive_after": engine.revive_after if engine is not None else getattr(vector_quantizer, "revive_after", None)})
     if is_main:
         os.makedirs(run_path, exist_ok=True)
@@ -193,7 +197,8 @@ def main():
           n_epochs=N_EPOCHS, vocab_size=VOCAB_SIZE, wandb_run=wandb_run, run_path=run_path, export_checkpoint=EXPORT_CHECKPOINT,
           max_length=TOKENIZED_SENTENCE_MAX_LENGTH, grad_sync=grad_sync, is_main=is_main, engine=engine,
           train_state_path=f"{run_path}/shelgon_train_state_last.pth" if EXPORT_TRAIN_STATE else None,
-          train_state_every=TRAIN_STATE_EVERY_EPOCHS, resume=resume, train_state_config=state_config, **weights)
+          train_state_every=TRAIN_STATE_EVERY_EPOCHS, resume=resume, train_state_config=state_config,
+          weight_ema_eval=WEIGHT_EMA_EVAL, **weights)
 
     # The test stage runs on EVERY rank (each on its shard of the test split): test() ends in the stage's all-reduce of the
     # statistics (Trainer._sum_over_ranks), a collective every rank has to enter.  Rank 0 wrote the checkpoint; agree() puts a
@@ -207,7 +212,9 @@ def main():
         test(prg=prg, console=console, device=device, dl_test=dl_test, n_batches_test=n_batches_test, model=model,
              tokenizer=tokenizer, tokenizer_add_special_tokens=TOKENIZER_ADD_SPECIAL_TOKENS, decoded_sentences=decoded_sentences,
              vocab_size=VOCAB_SIZE, epoch=N_EPOCHS, wandb_run=wandb_run, max_length=TOKENIZED_SENTENCE_MAX_LENGTH, engine=engine,
-             **weights)
+             # weight_ema: with WEIGHT_EMA_EVAL the checkpoint just loaded was written under the average and HOLDS the averaged
+             # weights that were scored -- they are tested as they are (the scope would put the last epoch's average in their place)
+             weight_ema_eval=False, **weights)
     decoded_sentences = ddp.gather_lists(decoded_sentences)      # every rank decoded its own shard: rank 0 writes them all
     if is_main:
         if prg is not None:
