@@ -195,6 +195,38 @@ int kvq_ce_backward_bias(const void* logits, const int64_t* target, const float*
                          int V, int64_t ld, int io_dtype, void* g_logits, float* bias_part, size_t part_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The same loss over the COUNTED rows only (F.cross_entropy's ignore_index).  Row n is IGNORED iff
+ * target[n] == ignore_index, which may lie outside [0, V) (e.g. -100); every other row is counted and must have 0 <= target < V.
+ *
+ *   counted row : row_loss / row_lse / pred / gradient exactly as in the entry points above
+ *   ignored row : row_loss = 0, row_lse = 0, pred = ignore_index, gradient row (padding columns included) = +0.  Nothing of its
+ *                 logits row is read -- not by the forward (no load at x[target]), not by the backward, not even in place -- so NaN
+ *                 or garbage there reaches no output.
+ *   count [1] f32 = number of counted rows, exact (N <= 2^24 is required) ; loss = sum(row_loss) / count ; acc = hits / count
+ *   count == 0  : loss = acc = count = 0 and every gradient is 0.  THIS DEVIATES FROM TORCH, which returns NaN for a batch
+ *                 without a counted target; a NaN here would poison the captured step's optimiser state.
+ *   backward    : g_logits[n,v] = g_loss / max(count, 1) * (softmax - onehot).  `count` is the DEVICE scalar the forward wrote;
+ *                 the host never sees it, so the pair can sit in a captured graph.
+ * Deterministic (no atomics, fixed summation order).  With no row ignored every output has the bits of the entry point above:
+ * count == N and g_loss / count is the same f32 division as g_loss / (float)N.
+ * loss, acc and count of the forwards may each be NULL; count of the backwards may not.
+ */
+int kvq_ce_forward_ignore(const void* logits, const int64_t* target, int64_t N, int V, int64_t ld, int io_dtype, int64_t ignore_index,
+                          float* row_loss, float* row_lse, int64_t* pred, float* loss, float* acc, float* count, void* stream);
+int kvq_ce_forward_stats_ignore(const void* logits, const int64_t* target, int64_t N, int64_t ld, int io_dtype, const float* stats,
+                                int tiles, int64_t ignore_index, float* row_loss, float* row_lse, int64_t* pred, float* loss,
+                                float* acc, float* count, void* stream);
+int kvq_ce_backward_ignore(const void* logits, const int64_t* target, const float* row_lse, const float* g_loss, const float* count,
+                           int64_t ignore_index, int64_t N, int V, int64_t ld, int io_dtype, void* g_logits, void* stream);
+/* An ignored row adds exactly 0 to bias_part. */
+int kvq_ce_backward_bias_ignore(const void* logits, const int64_t* target, const float* row_lse, const float* g_loss,
+                                const float* count, int64_t ignore_index, int64_t N, int V, int64_t ld, int io_dtype, void* g_logits,
+                                float* bias_part, size_t part_bytes, void* stream);
+/* per_sentence[b] = hits over sentence b's counted tokens / their number; 0 for a sentence without a counted token. */
+int kvq_seq_acc_ignore(const int64_t* pred, const int64_t* target, int64_t B, int S, int64_t ignore_index, float* per_sentence,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Memory-bound pieces of the BERT blocks (HuggingFace modeling_bert.py as used by models/bagon/Bagon.py:24-31),
  * one kernel pass per block boundary; bf16 or f32 activations, f32 arithmetic.  `seed`/`site` key the counter-based
  * dropout generator (Philox4x32-10): forward and backward regenerate the same mask, nothing is stored.

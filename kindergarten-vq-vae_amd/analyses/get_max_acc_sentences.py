@@ -8,6 +8,9 @@ input_sentence, renumbers them (the old index stays as the column "index", as re
     <RUN_DIR>/decoded_sentences_max_acc_only.md
     <RUN_DIR>/decoded_sentences_max_acc_only.feather      (.csv when feather is unavailable)
 -- the table analyses/latent_arithmetics/ and analyses/latent_traversals/ start from.  Host work only.
+sentence_acc is the per-sentence accuracy the run's step reported: with LOSS_IGNORE_PAD / KVQ_LOSS_IGNORE_PAD=1 (DESIGN.md section
+5g) that is the accuracy over the sentence's real tokens, so the filter then keeps the sentences whose WORDS were all reconstructed;
+nothing changes here.
 Constants can be overridden from the environment as KVQ_<NAME>=<python literal>, as in models/shelgon3/config.py.
 """
 import ast

@@ -17,6 +17,8 @@ What differs:
 Without <RUN_DIR>/decoded_sentences_max_acc_only.* the table is built from the dSentences corpus and its factor labels (written
 synthetically when absent), as the other analyses do.
 Constants can be overridden from the environment as KVQ_<NAME>=<python literal>, as in models/shelgon3/config.py.
+With KVQ_LOSS_IGNORE_PAD=1 the engine behind model.decode_latents scores real tokens only: acc / acc_per_sentence
+of decode() are then real-token accuracies and recon_ids carries the pad id at pads; nothing changes here.
 """
 import ast
 import os

@@ -12,6 +12,9 @@ Result file (the reference prints): <RESULTS_DIR>/code_traversal.feather (.csv w
 (sentence, position, code): input_sentence, position, code, own_code (bool), recon_sentence, n_changed_tokens.
 Without <RUN_DIR>/decoded_sentences_max_acc_only.* the sentences come from the dSentences corpus and its factor labels.
 Constants can be overridden from the environment as KVQ_<NAME>=<python literal>, as in models/shelgon3/config.py.
+With KVQ_LOSS_IGNORE_PAD=1 the engine behind model.traverse_codes / decode_codes scores real tokens only: the
+decoded rows carry the pad id at the sentence's pads (so n_changed_tokens counts words), accuracies are real-token accuracies;
+nothing changes here.
 """
 import ast
 import os

@@ -66,6 +66,10 @@ SIGNATURES = {
     "kvq_ce_backward": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _i64, _int, _vp, _vp]),
     "kvq_ce_bwd_partial_rows": (_i64, [_i64]),
     "kvq_ce_backward_bias": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _i64, _int, _vp, _vp, _sz, _vp]),
+    "kvq_ce_forward_ignore": (_int, [_vp, _vp, _i64, _int, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "kvq_seq_acc_ignore": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _vp]),
+    "kvq_ce_backward_ignore": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _i64, _int, _vp, _vp]),
+    "kvq_ce_backward_bias_ignore": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _i64, _int, _vp, _vp, _sz, _vp]),
     "kvq_dropout_residual_ln_fwd": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _f32, _f32, C.c_uint64, C.c_uint32, _int, _vp, _vp, _vp, _vp, _vp]),
     "kvq_ln_bwd_workspace_bytes": (_sz, [_i64, _int]),
     "kvq_dropout_residual_ln_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _f32, C.c_uint64, C.c_uint32, _int, _vp, _vp, _vp, _vp, _vp,
@@ -124,6 +128,7 @@ SIGNATURES = {
     "kvq_attn_set_variant": (_int, [_int]),
     "kvq_adam_step": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f32, _f32, _f32, _f32, _f32, _i64, _f32, _vp]),
     "kvq_ce_forward_stats": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "kvq_ce_forward_stats_ignore": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kvq_gemm_ce_stats_bytes": (_sz, [_int, _int]),
     "kvq_gemm_bf16_ce": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _vp, _sz, _vp]),
     "kvq_step_state_advance": (_int, [_vp, _f32, _f32, C.POINTER(_i64), _int, _f32, _f32, _vp]),

@@ -290,7 +290,8 @@ class _StepGraphs:
         self.sorted = (srt, perm)
         self.z_q = torch.empty((N, H), dtype=eng.dtype, device=dev)
         self.idx = torch.empty(N * max(eng.G, 1), dtype=torch.int64, device=dev)
-        self.scal = torch.zeros(4, dtype=torch.float32, device=dev)         # loss, accuracy | quantiser loss, perplexity: one clone per step
+        # loss, accuracy | quantiser loss, perplexity | counted tokens (loss_ignore_pad; 0 otherwise): one clone per step
+        self.scal = torch.zeros(5, dtype=torch.float32, device=dev)
         self.vq_out = self.scal[2:4]
         # keep_graph: the captured hipGraph_t stays readable behind the executable one (node_census; a few hundred nodes)
         self.graphs, self.inter = [torch.cuda.CUDAGraph(keep_graph=True)], []
@@ -404,8 +405,9 @@ class TrainEngine:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
                  milestones=None, gamma=0.1, loss_recon_scale=1.0, loss_vq_scale=1.0, seed=1234,
                  bucket_mib=64, process_group=None, fp8_forward=None, fp8_backward=None, max_grad_norm=None, grad_accum=None,
-                 weight_ema=None):
+                 weight_ema=None, loss_ignore_pad=None):
         self.model = model
+        self.loss_ignore_pad = self.check_loss_ignore_pad(loss_ignore_pad, env=True)
         self.grad_accum = self.check_grad_accum(grad_accum, env=True)
         self.max_grad_norm = self.check_max_grad_norm(max_grad_norm, env=True)     # (before anything is laid out: a bad value changes nothing)
         self.weight_ema = self.check_weight_ema(weight_ema, env=True)
@@ -553,6 +555,11 @@ class TrainEngine:
         if len(pads) != 1:
             raise KvqError("TrainEngine expects the same padding_idx in the encoder and decoder word embeddings")
         self._pad_idx = pads.pop()
+        # option, off by default: reconstruction loss, accuracy and per-sentence accuracy over the tokens whose
+        # target is not the pad id (F.cross_entropy's ignore_index) -- the kvq_*_ignore twins of the loss kernels, one for one
+        if self.loss_ignore_pad and self._pad_idx is None:
+            raise KvqError("TrainEngine: loss_ignore_pad (KVQ_LOSS_IGNORE_PAD) needs word embeddings with a padding_idx: there is no "
+                           "pad id to leave out of the loss")
         self.n_enc_layers = len(enc.encoder.layer)
         self.n_dec_layers = len(dec.bert.encoder.layer)
         self.nh = self.ecfg.num_attention_heads
@@ -1455,7 +1462,9 @@ class TrainEngine:
                          want_logits=False, quantizer_training=None, stop_after_quantizer=False, defer_backward=False, target_ids=None,
                          latents=None, stop_after_encoder=False, skip_quantizer=False, want_latents=False):
         """Forward (+ backward when compute_grads).  Returns dict(loss_recon, loss_vq, perplexity, acc, acc_per_sentence,
-        recon_ids, indices [, logits]).  dec_ids / dec_mask: the decoder's own input (Bagon.forward takes one, and the Bagon step
+        recon_ids, indices [, logits] [, loss_tokens]).  loss_ignore_pad: loss_recon, its gradient, acc and
+        acc_per_sentence run over the positions whose target is not the pad id, loss_tokens is their number (a device scalar) and
+        recon_ids carries the pad id at the others.  dec_ids / dec_mask: the decoder's own input (Bagon.forward takes one, and the Bagon step
         tokenises and perturbs the two sides separately, models/bagon/Trainer.py:78-96; default = the encoder's).  target_ids:
         what the loss and the accuracy score the logits against (default = the decoder's input, as models/bagon/Trainer.py:103-110
         and models/shelgon3/Trainer.py:94-101 do).
@@ -1655,7 +1664,7 @@ class TrainEngine:
         out = self.forward_backward(None, None, training=False, compute_grads=False, dec_ids=dec_ids, dec_mask=dec_mask,
                                     want_logits=want_logits, quantizer_training=False, target_ids=target_ids, latents=latents,
                                     skip_quantizer=not quantize)
-        res = {k: out[k] for k in ("recon_ids", "acc", "acc_per_sentence", "loss_recon")}
+        res = {k: out[k] for k in ("recon_ids", "acc", "acc_per_sentence", "loss_recon") + (("loss_tokens",) if "loss_tokens" in out else ())}
         if want_logits:
             res["logits"] = out["logits"]
         if quantize:
@@ -1873,9 +1882,23 @@ class TrainEngine:
         row_loss = torch.empty(Nd, dtype=torch.float32, device=self.dev)
         row_lse = torch.empty(Nd, dtype=torch.float32, device=self.dev)
         pred = torch.empty(Nd, dtype=torch.int64, device=self.dev)
-        ce_out = self._cap.scal[0:2] if (self._cap is not None and compute_grads) else torch.empty(2, dtype=torch.float32, device=self.dev)
+        ign = self._pad_idx if self.loss_ignore_pad else None      # loss_ignore_pad: rows whose target is the pad id are left out
+        ce_cnt = None
+        if self._cap is not None and compute_grads:
+            ce_out = self._cap.scal[0:2]
+            if ign is not None:
+                ce_cnt = self._cap.scal[4:5]
+        elif ign is not None:
+            ce_out = torch.empty(3, dtype=torch.float32, device=self.dev)
+            ce_cnt = ce_out[2:3]
+        else:
+            ce_out = torch.empty(2, dtype=torch.float32, device=self.dev)
         if lm_stats is not None:
-            nnops.ce_forward_stats(logits, tgt, lm_stats, row_loss, row_lse, pred, ce_out[0:], ce_out[1:])
+            nnops.ce_forward_stats(logits, tgt, lm_stats, row_loss, row_lse, pred, ce_out[0:], ce_out[1:], ignore_index=ign, count=ce_cnt)
+        elif ign is not None:
+            check(lib().kvq_ce_forward_ignore(logits.data_ptr(), tgt.data_ptr(), Nd, self.V, self.Vp, self.io, ign, row_loss.data_ptr(),
+                                              row_lse.data_ptr(), pred.data_ptr(), ce_out[0:].data_ptr(), ce_out[1:].data_ptr(),
+                                              ce_cnt.data_ptr(), stream_ptr()), "kvq_ce_forward_ignore")
         else:
             check(lib().kvq_ce_forward(logits.data_ptr(), tgt.data_ptr(), Nd, self.V, self.Vp, self.io, row_loss.data_ptr(),
                                        row_lse.data_ptr(), pred.data_ptr(), ce_out[0:].data_ptr(), ce_out[1:].data_ptr(), stream_ptr()),
@@ -1883,10 +1906,16 @@ class TrainEngine:
         acc_sent = None
         if self.sentence_acc or latents is not None:     # seq_acc's second result (common/metrics.py:32-36), read by the Bagon trainer's decode step
             acc_sent = torch.empty(B, dtype=torch.float32, device=self.dev)
-            check(lib().kvq_seq_acc(pred.data_ptr(), tgt.data_ptr(), B, Sd, acc_sent.data_ptr(), stream_ptr()), "kvq_seq_acc")
+            if ign is not None:
+                check(lib().kvq_seq_acc_ignore(pred.data_ptr(), tgt.data_ptr(), B, Sd, ign, acc_sent.data_ptr(), stream_ptr()),
+                      "kvq_seq_acc_ignore")
+            else:
+                check(lib().kvq_seq_acc(pred.data_ptr(), tgt.data_ptr(), B, Sd, acc_sent.data_ptr(), stream_ptr()), "kvq_seq_acc")
         out = dict(loss_recon=ce_out[0] if self.w_recon == 1.0 else ce_out[0] * self.w_recon,
                    loss_vq=(loss_vq if self.w_vq == 1.0 else loss_vq * self.w_vq) if loss_vq is not None else None,
                    perplexity=perplexity, acc=ce_out[1], acc_per_sentence=acc_sent, recon_ids=pred.view(B, Sd), indices=indices)
+        if ign is not None:
+            out["loss_tokens"] = ce_cnt[0]                        # the number of counted tokens, a device scalar (f32, exact)
         if want_logits:
             out["logits"] = logits[:, :self.V].reshape(B, Sd, self.V)
             out["loss_vq_raw"] = loss_vq                          # without the trainer's loss weight
@@ -1909,14 +1938,24 @@ class TrainEngine:
         elif tr["head.bias"] and self.Vp % 8 == 0:
             # in place: logits := d loss / d logits; the LM-head bias gradient leaves the same pass as partial column sums
             pb = torch.empty((lib().kvq_ce_bwd_partial_rows(Nd), self.Vp), dtype=torch.float32, device=self.dev)
-            check(lib().kvq_ce_backward_bias(logits.data_ptr(), tgt.data_ptr(), row_lse.data_ptr(), g_scale.data_ptr(), Nd, self.V,
-                                             self.Vp, self.io, logits.data_ptr(), pb.data_ptr(), pb.numel() * 4, stream_ptr()),
-                  "kvq_ce_backward_bias")
+            if ign is not None:         # the count is read from the slot the forward's finalize wrote, on the device
+                check(lib().kvq_ce_backward_bias_ignore(logits.data_ptr(), tgt.data_ptr(), row_lse.data_ptr(), g_scale.data_ptr(),
+                                                        ce_cnt.data_ptr(), ign, Nd, self.V, self.Vp, self.io, logits.data_ptr(),
+                                                        pb.data_ptr(), pb.numel() * 4, stream_ptr()), "kvq_ce_backward_bias_ignore")
+            else:
+                check(lib().kvq_ce_backward_bias(logits.data_ptr(), tgt.data_ptr(), row_lse.data_ptr(), g_scale.data_ptr(), Nd, self.V,
+                                                 self.Vp, self.io, logits.data_ptr(), pb.data_ptr(), pb.numel() * 4, stream_ptr()),
+                      "kvq_ce_backward_bias")
             self._defer(pb, fl.g("head.bias", rows=self.Vp), pb.shape[0], self.Vp, self.Vp)
             g_logits = logits
         else:
-            check(lib().kvq_ce_backward(logits.data_ptr(), tgt.data_ptr(), row_lse.data_ptr(), g_scale.data_ptr(), Nd, self.V, self.Vp,
-                                        self.io, logits.data_ptr(), stream_ptr()), "kvq_ce_backward")      # in place
+            if ign is not None:
+                check(lib().kvq_ce_backward_ignore(logits.data_ptr(), tgt.data_ptr(), row_lse.data_ptr(), g_scale.data_ptr(),
+                                                   ce_cnt.data_ptr(), ign, Nd, self.V, self.Vp, self.io, logits.data_ptr(),
+                                                   stream_ptr()), "kvq_ce_backward_ignore")                # in place
+            else:
+                check(lib().kvq_ce_backward(logits.data_ptr(), tgt.data_ptr(), row_lse.data_ptr(), g_scale.data_ptr(), Nd, self.V, self.Vp,
+                                            self.io, logits.data_ptr(), stream_ptr()), "kvq_ce_backward")      # in place
             g_logits = logits
             if tr["head.bias"]:
                 self._defer_colsum(g_logits, fl.g("head.bias", rows=self.Vp))
@@ -2200,6 +2239,22 @@ class TrainEngine:
         return v
 
     @staticmethod
+    def check_loss_ignore_pad(v, env=False):
+        """The bool a TrainEngine(loss_ignore_pad=...) accepts (False: off); anything else raises KvqError.  env: None means
+        KVQ_LOSS_IGNORE_PAD from the environment (unset, empty or 0: off; 1: on).  That the model has a pad id is checked by the
+        constructor, which knows the model."""
+        if v is None and env and os.environ.get("KVQ_LOSS_IGNORE_PAD", "") != "":
+            s = os.environ["KVQ_LOSS_IGNORE_PAD"]
+            if s not in ("0", "1"):
+                raise KvqError(f"TrainEngine: KVQ_LOSS_IGNORE_PAD (loss_ignore_pad) must be 0 or 1, got {s!r}")
+            v = s == "1"
+        if v is None:
+            return False
+        if not isinstance(v, bool):
+            raise KvqError(f"TrainEngine: loss_ignore_pad must be None, False or True, got {v!r}")
+        return v
+
+    @staticmethod
     def check_weight_ema(v, env=False):
         """None (off), or the float in (0, 1) a TrainEngine(weight_ema=...) accepts; anything else raises KvqError.
         env: None means KVQ_WEIGHT_EMA from the environment (unset or empty: off)."""
@@ -2472,6 +2527,7 @@ class TrainEngine:
             "w8_keys": list(self._w8_index) if self.fp8 else [],
             "world": int(self.world),
             **({"weight_ema": float(self.weight_ema)} if self.weight_ema is not None else {}),     # off: exactly the keys of before
+            **({"loss_ignore_pad": True} if self.loss_ignore_pad else {}),
         }
 
     def _state_slots(self, present) -> dict:

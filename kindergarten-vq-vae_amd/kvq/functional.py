@@ -353,10 +353,12 @@ def gumbel_quantize(logits: torch.Tensor, tau: float, hard: bool, kld_scale: flo
 
 class _FusedCE(torch.autograd.Function):
     """logits[N,V], target[N] -> loss (mean CE), acc (token accuracy), pred[N].  Backward overwrites `logits`
-    with its gradient in place when `inplace_backward` (saves N*V elements; the logits are dead by then)."""
+    with its gradient in place when `inplace_backward` (saves N*V elements; the logits are dead by then).
+    ignore_index (None: off): rows whose target equals it are not read, get a zero gradient, and loss / acc are means over the
+    other rows (kvq_ce_forward_ignore); their number stays on the device for the backward."""
 
     @staticmethod
-    def forward(ctx, logits, target, inplace_backward):
+    def forward(ctx, logits, target, inplace_backward, ignore_index=None):
         require_gpu(logits, target)
         if not logits.is_contiguous():
             raise _ffi.KvqError("fused_cross_entropy: logits must be contiguous")
@@ -366,11 +368,18 @@ class _FusedCE(torch.autograd.Function):
         row_loss = torch.empty(N, dtype=torch.float32, device=dev)
         row_lse = torch.empty(N, dtype=torch.float32, device=dev)
         pred = torch.empty(N, dtype=torch.int64, device=dev)
-        out = torch.empty(2, dtype=torch.float32, device=dev)
-        check(lib().kvq_ce_forward(logits.data_ptr(), target.data_ptr(), N, V, V, io_dtype_of(logits), row_loss.data_ptr(),
-                                   row_lse.data_ptr(), pred.data_ptr(), out[0:].data_ptr(), out[1:].data_ptr(),
-                                   stream_ptr()), "kvq_ce_forward")
-        ctx.save_for_backward(logits, target, row_lse)
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        if ignore_index is None:
+            check(lib().kvq_ce_forward(logits.data_ptr(), target.data_ptr(), N, V, V, io_dtype_of(logits), row_loss.data_ptr(),
+                                       row_lse.data_ptr(), pred.data_ptr(), out[0:].data_ptr(), out[1:].data_ptr(),
+                                       stream_ptr()), "kvq_ce_forward")
+            ctx.save_for_backward(logits, target, row_lse)
+        else:
+            check(lib().kvq_ce_forward_ignore(logits.data_ptr(), target.data_ptr(), N, V, V, io_dtype_of(logits), int(ignore_index),
+                                              row_loss.data_ptr(), row_lse.data_ptr(), pred.data_ptr(), out[0:].data_ptr(),
+                                              out[1:].data_ptr(), out[2:].data_ptr(), stream_ptr()), "kvq_ce_forward_ignore")
+            ctx.save_for_backward(logits, target, row_lse, out[2:])
+        ctx.ignore_index = None if ignore_index is None else int(ignore_index)
         ctx.inplace = bool(inplace_backward)
         loss, acc = out[0], out[1]
         ctx.mark_non_differentiable(acc, pred)
@@ -378,18 +387,29 @@ class _FusedCE(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _ga, _gp):
-        logits, target, row_lse = ctx.saved_tensors
+        logits, target, row_lse = ctx.saved_tensors[:3]
         N, V = logits.shape
         g = logits if ctx.inplace else torch.empty_like(logits)
         g_loss = g_loss.contiguous().float()
-        check(lib().kvq_ce_backward(logits.data_ptr(), target.data_ptr(), row_lse.data_ptr(), g_loss.data_ptr(), N, V, V,
-                                    io_dtype_of(logits), g.data_ptr(), stream_ptr()), "kvq_ce_backward")
-        return g, None, None
+        if ctx.ignore_index is None:
+            check(lib().kvq_ce_backward(logits.data_ptr(), target.data_ptr(), row_lse.data_ptr(), g_loss.data_ptr(), N, V, V,
+                                        io_dtype_of(logits), g.data_ptr(), stream_ptr()), "kvq_ce_backward")
+        else:
+            count = ctx.saved_tensors[3]
+            check(lib().kvq_ce_backward_ignore(logits.data_ptr(), target.data_ptr(), row_lse.data_ptr(), g_loss.data_ptr(),
+                                               count.data_ptr(), ctx.ignore_index, N, V, V, io_dtype_of(logits), g.data_ptr(),
+                                               stream_ptr()), "kvq_ce_backward_ignore")
+        return g, None, None, None
 
 
-def fused_cross_entropy(logits: torch.Tensor, target: torch.Tensor, inplace_backward: bool = False):
-    """Trainer.py:94-101 in one pass: (loss_recon, acc_per_batch, recon_ids).  logits [..., V], target [...]."""
+def fused_cross_entropy(logits: torch.Tensor, target: torch.Tensor, inplace_backward: bool = False, ignore_index=None):
+    """Trainer.py:94-101 in one pass: (loss_recon, acc_per_batch, recon_ids).  logits [..., V], target [...].
+    ignore_index (None: off; may lie outside [0, V), e.g. -100): loss and accuracy are means over the positions whose target differs
+    from it, as F.cross_entropy(ignore_index=...) takes them; recon_ids carries ignore_index at the ignored positions.  Unlike
+    torch, a target without a counted position gives loss = acc = 0 and a zero gradient, not NaN."""
     V = logits.shape[-1]
     shape = target.shape
-    loss, acc, pred = _FusedCE.apply(logits.reshape(-1, V), target, inplace_backward)
+    if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)):
+        raise _ffi.KvqError(f"fused_cross_entropy: ignore_index must be None or an int, got {ignore_index!r}")
+    loss, acc, pred = _FusedCE.apply(logits.reshape(-1, V), target, inplace_backward, ignore_index)
     return loss, acc, pred.reshape(shape)

@@ -795,9 +795,16 @@ def gemm_ce(x, w, bias, V):
     return logits, stats
 
 
-def ce_forward_stats(logits, target, stats, row_loss, row_lse, pred, loss, acc):
-    """kvq_ce_forward's outputs from gemm_ce()'s statistics (reads one logit per row)."""
+def ce_forward_stats(logits, target, stats, row_loss, row_lse, pred, loss, acc, ignore_index=None, count=None):
+    """kvq_ce_forward's outputs from gemm_ce()'s statistics (reads one logit per row).  ignore_index: the means run over the rows
+    whose target differs from it, and `count` [1] f32 receives their number (kvq_ce_forward_stats_ignore)."""
     N = logits.shape[0]
+    if ignore_index is not None:
+        check(lib().kvq_ce_forward_stats_ignore(logits.data_ptr(), target.data_ptr(), N, logits.stride(0), io_dtype_of(logits),
+                                                stats.data_ptr(), stats.shape[1], int(ignore_index), row_loss.data_ptr(),
+                                                row_lse.data_ptr(), pred.data_ptr(), _p(loss), _p(acc), _p(count), stream_ptr()),
+              "kvq_ce_forward_stats_ignore")
+        return
     check(lib().kvq_ce_forward_stats(logits.data_ptr(), target.data_ptr(), N, logits.stride(0), io_dtype_of(logits), stats.data_ptr(),
                                      stats.shape[1], row_loss.data_ptr(), row_lse.data_ptr(), pred.data_ptr(), _p(loss), _p(acc),
                                      stream_ptr()), "kvq_ce_forward_stats")

@@ -156,14 +156,17 @@ class Bagon(nn.Module):
         return engine_of(self).decode(latents, decoder_input_ids, decoder_attention_mask, target_ids=target_ids, quantize=quantize,
                                       want_logits=want_logits)
 
-    def forward_loss(self, encoder_input_ids, encoder_attention_mask, decoder_input_ids, decoder_attention_mask):
+    loss_ignore_index = None     # LOSS_IGNORE_PAD on the autograd path: main.py puts the pad id here, the trainer's step hands it to forward_loss
+
+    def forward_loss(self, encoder_input_ids, encoder_attention_mask, decoder_input_ids, decoder_attention_mask, ignore_index=None):
         """Fused step body of the plain autoencoder: (loss_recon, acc_per_batch, recon_ids) -- the loss block of
-        models/bagon/Trainer.py:103-110 in one pass over the logits."""
+        models/bagon/Trainer.py:103-110 in one pass over the logits.  ignore_index: fused_cross_entropy's (the pad id: loss and
+        accuracy over the real tokens)."""
         from kvq.functional import fused_cross_entropy
         enc = self.encode(encoder_input_ids, encoder_attention_mask)
         hidden = self.decode_hidden(enc, decoder_input_ids, decoder_attention_mask)
         logits = kbert.lm_head_logits(self.decoder, hidden, self.compute_dtype)
-        return fused_cross_entropy(logits, decoder_input_ids, inplace_backward=True)
+        return fused_cross_entropy(logits, decoder_input_ids, inplace_backward=True, ignore_index=ignore_index)
 
     # ---- bookkeeping ---------------------------------------------------------------------------------------------
     def _summary_parts(self):

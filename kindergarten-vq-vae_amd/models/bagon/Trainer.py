@@ -74,9 +74,14 @@ def step(device, model, tokenizer_encoder, tokenizer_decoder,
             out = engine.eval_step(input_ids_encoder, attention_mask_encoder, **dec)
         loss_recon_step, acc_batch, acc_sentence, recon_ids = out["loss_recon"], out["acc"], out["acc_per_sentence"], out["recon_ids"]
     else:
+        pad = getattr(model, "loss_ignore_index", None)                                           # LOSS_IGNORE_PAD: the pad id
         loss_recon_step, acc_batch, recon_ids = model.forward_loss(input_ids_encoder, attention_mask_encoder,
-                                                                   input_ids_decoder, attention_mask_decoder)
-        acc_sentence = torch.eq(recon_ids, input_ids_decoder).to(torch.float32).mean(dim=-1)      # common/metrics.py:32
+                                                                   input_ids_decoder, attention_mask_decoder, ignore_index=pad)
+        if pad is None:
+            acc_sentence = torch.eq(recon_ids, input_ids_decoder).to(torch.float32).mean(dim=-1)  # common/metrics.py:32
+        else:                                                                                      # over the sentence's real tokens; none: 0
+            real = input_ids_decoder != pad
+            acc_sentence = (torch.eq(recon_ids, input_ids_decoder) & real).sum(dim=-1) / real.sum(dim=-1).clamp(min=1)
         if opt is not None:                                                                        # Trainer.py:115-122
             grad_sync.zero_grad() if grad_sync is not None else opt.zero_grad()
             loss_recon_step.backward()
@@ -103,6 +108,8 @@ def step(device, model, tokenizer_encoder, tokenizer_decoder,
 
 
 def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batch: int):
+    # LOSS_IGNORE_PAD: a step's loss and accuracy are then means over its real tokens, but the epoch means below stay weighted by
+    # SENTENCES (n_els_batch), as before -- not by out["loss_tokens"]
     stats_stage_run["loss_recon_run"] += stats_step["loss_recon_step"] * n_els_batch
     stats_stage_run["loss_full_run"] += stats_step["loss_full_step"] * n_els_batch
     stats_stage_run["metric_acc_run"] += stats_step["metric_acc_step_per_batch"] * n_els_batch * 1e2

@@ -54,6 +54,7 @@ MAX_GRAD_NORM = None            # None (off) | float > 0 | float("inf"): the eng
 GRAD_ACCUM_STEPS = 1            # int >= 1: train_step calls (micro-batches) per optimiser step -- the engine sums their gradients in f32 and Adam reads the mean; MILESTONES, engine.step_count and the bias corrections count OPTIMISER steps, perf/train_steps counts calls; KVQ_GRAD_ACCUM; DESIGN.md section 5d
 WEIGHT_EMA_DECAY = None       # None (off) | float in (0, 1): the engine keeps an f32 moving average of the trained weights, updated behind Adam inside the step (the decay warms up as min(decay, (1 + t) / (10 + t))); KVQ_WEIGHT_EMA; DESIGN.md section 5f
 WEIGHT_EMA_EVAL = True         # with WEIGHT_EMA_DECAY: validation, the best-val checkpoints and the test stage run under the average (False: the average is kept and saved with the training state, evaluation reads the live weights)
+LOSS_IGNORE_PAD = False        # False | True: the engine step takes the reconstruction loss, the accuracy and the per-sentence accuracy over the tokens whose target is not the pad id (F.cross_entropy's ignore_index) instead of over all B*S positions; KVQ_LOSS_IGNORE_PAD; DESIGN.md section 5g
 
 RUNS_DIR = "./runs/Bagon"
 EXPORT_CHECKPOINT = True
@@ -100,6 +101,12 @@ if WEIGHT_EMA_DECAY is not None and (isinstance(WEIGHT_EMA_DECAY, bool) or not i
     raise ValueError(f"WEIGHT_EMA_DECAY (KVQ_WEIGHT_EMA) must be None or a float in (0, 1), got {WEIGHT_EMA_DECAY!r}")
 if not isinstance(WEIGHT_EMA_EVAL, bool):
     raise ValueError(f"WEIGHT_EMA_EVAL (KVQ_WEIGHT_EMA_EVAL) must be True or False, got {WEIGHT_EMA_EVAL!r}")
+if isinstance(LOSS_IGNORE_PAD, str) and not LOSS_IGNORE_PAD.strip():      # KVQ_LOSS_IGNORE_PAD= (empty) = unset, as TrainEngine reads the variable
+    LOSS_IGNORE_PAD = False
+if LOSS_IGNORE_PAD in (0, 1) and not isinstance(LOSS_IGNORE_PAD, bool) and _os.environ.get("KVQ_LOSS_IGNORE_PAD", "").strip() in ("0", "1"):
+    LOSS_IGNORE_PAD = bool(LOSS_IGNORE_PAD)      # the environment spells the switch 0 / 1, as TrainEngine reads it
+if not isinstance(LOSS_IGNORE_PAD, bool):
+    raise ValueError(f"LOSS_IGNORE_PAD (KVQ_LOSS_IGNORE_PAD) must be True or False (0 or 1 in the environment), got {LOSS_IGNORE_PAD!r}")
 if isinstance(TRAIN_STATE_EVERY_EPOCHS, bool) or not isinstance(TRAIN_STATE_EVERY_EPOCHS, int) or TRAIN_STATE_EVERY_EPOCHS < 1:
     raise ValueError(f"TRAIN_STATE_EVERY_EPOCHS (KVQ_TRAIN_STATE_EVERY_EPOCHS) must be an integer >= 1, got {TRAIN_STATE_EVERY_EPOCHS!r}")
 if isinstance(RESUME_FROM, str) and not RESUME_FROM.strip():      # KVQ_RESUME_FROM= (empty) = unset

@@ -96,7 +96,8 @@ def main():
                              fp8_backward=FP8_BACKWARD if FP8_BACKWARD else None,     # (None: KVQ_FP8_BACKWARD)
                              max_grad_norm=MAX_GRAD_NORM,                             # (None: off, or KVQ_MAX_GRAD_NORM)
                              grad_accum=GRAD_ACCUM_STEPS,                             # (1: off; the configuration has read KVQ_GRAD_ACCUM)
-                             weight_ema=WEIGHT_EMA_DECAY)                             # (None: off; the configuration has read KVQ_WEIGHT_EMA)
+                             weight_ema=WEIGHT_EMA_DECAY,                             # (None: off; the configuration has read KVQ_WEIGHT_EMA)
+                             loss_ignore_pad=LOSS_IGNORE_PAD)                         # (the configuration has read KVQ_LOSS_IGNORE_PAD)
         if TOKEN_CACHE and same_tok:
             for c in caches:
                 c.packed_pad_id = engine.pad_idx if not any_perturb else "off"     # perturbed ids are sorted by the engine itself
@@ -104,6 +105,10 @@ def main():
         grad_sync = ddp.GradSync(model.parameters(), bucket_mib=GRAD_BUCKET_MIB)
     if engine is None and GRAD_ACCUM_STEPS > 1:      # the autograd path steps its optimiser per batch: no silent batch of another size
         raise SystemExit("GRAD_ACCUM_STEPS > 1 (KVQ_GRAD_ACCUM) needs the engine (USE_ENGINE and a model shape it supports)")
+    if engine is None and LOSS_IGNORE_PAD:      # the autograd path: forward_loss hands the pad id to fused_cross_entropy(ignore_index=...)
+        model.loss_ignore_index = model.decoder.bert.embeddings.word_embeddings.padding_idx
+        if model.loss_ignore_index is None:
+            raise SystemExit("LOSS_IGNORE_PAD (KVQ_LOSS_IGNORE_PAD) needs word embeddings with a padding_idx")
     if engine is None and WEIGHT_EMA_DECAY is not None:      # the average is built inside the engine's step: no silent run without it
         raise SystemExit("WEIGHT_EMA_DECAY (KVQ_WEIGHT_EMA) needs the engine (USE_ENGINE and a model shape it supports)")
 
@@ -145,7 +150,8 @@ def main():
     run_conf.update({"n_params": model.model_params_summary_dict(), "optimizer": str(opt), "run_id": run_id, "world_size": world,
                      "grad_accum": engine.grad_accum if engine is not None else 1,
                      "max_grad_norm": engine.max_grad_norm if engine is not None else None,      # what the step really runs with
-                     "weight_ema": engine.weight_ema if engine is not None else None})
+                     "weight_ema": engine.weight_ema if engine is not None else None,
+                     "loss_ignore_pad": engine.loss_ignore_pad if engine is not None else model.loss_ignore_index is not None})
     if is_main:
         os.makedirs(run_path, exist_ok=True)
         if resume is None:                    # (a resumed run leaves the stored run's run_conf.json as it is)

@@ -98,13 +98,13 @@ class Shelgon(Bagon):
         return engine_of(self).traverse_codes(input_ids, attention_mask, sentence, position, dec_ids=decoder_input_ids,
                                               dec_mask=decoder_attention_mask, factor=factor)
 
-    def forward_loss(self, input_ids, attention_mask):
+    def forward_loss(self, input_ids, attention_mask, ignore_index=None):
         """Fused step body: (vq_loss, perplexity, indices, loss_recon, acc_per_batch, recon_ids)."""
         embeds = self.encode(input_ids, attention_mask)
         vq_loss, z_q, perplexity, indices = self._quantize(embeds, None)
         hidden = self.decode_hidden(z_q, input_ids, attention_mask)
         logits = kbert.lm_head_logits(self.decoder, hidden, self.compute_dtype)
-        loss_recon, acc, recon_ids = fused_cross_entropy(logits, input_ids, inplace_backward=True)
+        loss_recon, acc, recon_ids = fused_cross_entropy(logits, input_ids, inplace_backward=True, ignore_index=ignore_index)
         return vq_loss, perplexity, indices, loss_recon, acc, recon_ids
 
     def _summary_parts(self):

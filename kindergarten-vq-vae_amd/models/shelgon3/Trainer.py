@@ -68,7 +68,7 @@ def step(device, model, tokenizer, tokenizer_add_special_tokens: bool, opt,
         return stats, input_ids, out["recon_ids"]
 
     loss_vq_step, metric_perp_step, _indices, loss_recon_step, acc_step, recon_ids = \
-        model.forward_loss(input_ids, attention_mask)
+        model.forward_loss(input_ids, attention_mask, ignore_index=getattr(model, "loss_ignore_index", None))      # LOSS_IGNORE_PAD: the pad id
 
     loss_recon_step = loss_recon_step * (loss_recon_rescale_factor * loss_recon_weight)      # Trainer.py:103
     loss_vq_step = loss_vq_step * (loss_vq_rescale_factor * loss_vq_weight)                  # Trainer.py:104
@@ -97,6 +97,8 @@ def step(device, model, tokenizer, tokenizer_add_special_tokens: bool, opt,
 
 
 def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batch: int):
+    # LOSS_IGNORE_PAD: a step's loss and accuracy are then means over its real tokens, but the epoch means below stay weighted by
+    # SENTENCES (n_els_batch), as before -- not by out["loss_tokens"]
     stats_stage_run["loss_recon_run"] += stats_step["loss_recon_step"] * n_els_batch
     stats_stage_run["loss_vq_run"] += stats_step["loss_vq_step"] * n_els_batch
     stats_stage_run["metric_perp_run"] += stats_step["metric_perp_step"] * n_els_batch
