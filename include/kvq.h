@@ -404,6 +404,12 @@ int kvq_gemm_bf16(const void* A, const void* B, const void* bias, void* C, int M
 int kvq_gemm_any_bf16(const void* A, const void* B, const void* bias, void* C, int M, int N, int K, int lda, int ldb, int ldc,
                       int layout, int accumulate, void* stream);
 int kvq_gemm_grouped_bf16(const kvq_gemm_problem* problems, int n_problems, int layout, int tile, void* stream);
+/* A grouped launch (layout KVQ_GEMM_TN only) whose problems carry their own tile: tiles[i] is KVQ_GEMM_TILE_256x256 or _128x256.
+ * One grid; the 256 x 256 tiles are numbered -- and so dispatched -- first.  Every output element is what kvq_gemm_grouped_bf16
+ * stores for the same problem and tile, bit for bit.  For an output of more than one but less than two rounds of 256 x 256
+ * tiles (the LM-head weight gradient): a row slice that fills the CUs once with 256 x 256 tiles, the remaining rows as
+ * 128 x 256 tiles in a second, shorter round.  Same limits as kvq_gemm_grouped_bf16 (16 problems). */
+int kvq_gemm_grouped_mixed_bf16(const kvq_gemm_problem* problems, const int* tiles, int n_problems, int layout, void* stream);
 /* BertIntermediate in one kernel (modeling_bert.py:325-337), layout NT: Hout = A.B^T + bias (kept for backward) and
  * Aout = gelu(Hout as rounded to bf16) -- exact-erf GELU (erf to 1.2e-7).  tile: KVQ_GEMM_TILE_256x192 or _128x256 (optionally
  * | KVQ_GEMM_PERSISTENT). */

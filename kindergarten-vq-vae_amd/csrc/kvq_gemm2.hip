@@ -775,6 +775,45 @@ __global__ __launch_bounds__(C::THREADS, C::MINW) void gemm2_kernel(Params P) {
     gemm2_tile<C, EPI>(P.p[ti.pi], ti, smem);
 }
 
+// Several problems of TWO tile shapes in one grid (kvq_gemm_grouped_mixed_bf16: the LM-head weight gradient as one full round of
+// CA tiles and a shorter round of CB tiles).  The host puts the CA problems first, so the tiles [0, nbig) of the launch are
+// CA's -- they are dispatched first -- and a workgroup knows its class from blockIdx alone: one scalar branch (uniform over the
+// whole workgroup) to the same gemm2_tile code the single-shape kernels run.  Each class is numbered by itself: XCD-aware over
+// its own tile count (block nbig + j of the second class sits on XCD (nbig + j) & 7, so blocks with equal j & 7 still share an
+// XCD and get one contiguous band), then the problem's band walk.  tile0 counts through both classes, so the problem look-up
+// is locate_tile's.
+__device__ __forceinline__ int xcd_number(int id, int nt) {
+    const int q = nt >> 3, r = nt & 7, x = id & 7;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (id >> 3);
+}
+template <class C>
+__device__ __forceinline__ TileId locate_tile_class(const Params& P, int id) {
+    int pi = 0;
+#pragma unroll
+    for (int i = 1; i < MAX_PROBLEMS; ++i)
+        if (i < P.nprob && id >= P.p[i].tile0) pi = i;
+    const Problem& pr = P.p[pi];
+    TileId t;
+    t.pi = pi;
+    band_walk(pr, id - pr.tile0, t.tm, t.tn);
+    t.m0 = t.tm * C::BM;
+    t.n0 = t.tn * C::BN;
+    return t;
+}
+template <class CA, class CB>
+__global__ __launch_bounds__(CA::THREADS, CA::MINW) void gemm2_mixed_kernel(Params P, int nbig) {
+    static_assert(CA::THREADS == CB::THREADS && CA::MINW == CB::MINW, "one workgroup shape for both tile classes");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int b = blockIdx.x;
+    if (b < nbig) {
+        const TileId ti = locate_tile_class<CA>(P, xcd_number(b, nbig));
+        gemm2_tile<CA, EPI_NONE>(P.p[ti.pi], ti, smem);
+    } else {
+        const TileId ti = locate_tile_class<CB>(P, nbig + xcd_number(b - nbig, P.ntiles - nbig));
+        gemm2_tile<CB, EPI_NONE>(P.p[ti.pi], ti, smem);
+    }
+}
+
 // ONE problem (every launch of the step but the grouped weight gradients).  What the workgroup needs before its first DMA --
 // the tile walk's constants, the operand and bias pointers, the leading dimensions, K, M, N -- are the FIRST 14 DWORDS of the kernel
 // arguments, as scalars (four pairs of 16-bit numbers packed; a problem with a number above 65535 takes gemm2_kernel): with -amdgpu-kernarg-preload-count they arrive in SGPRs with the
@@ -1380,6 +1419,48 @@ int kvq_gemm_grouped_bf16(const kvq_gemm_problem* probs, int nprob, int layout, 
         case KVQ_GEMM_TILE_128x192H: return g2::launch_layout<g2::Cfg128x192h>(layout, P, st);
         default: return g2::launch_layout<g2::Cfg128x192>(layout, P, st);
     }
+}
+
+int kvq_gemm_grouped_mixed_bf16(const kvq_gemm_problem* probs, const int* tiles, int nprob, int layout, void* stream) {
+    const char* who = "kvq_gemm_grouped_mixed_bf16";
+    KVQ_REQUIRE(probs && tiles && nprob >= 1 && nprob <= g2::MAX_PROBLEMS, "%s: 1..%d problems per launch", who, g2::MAX_PROBLEMS);
+    KVQ_REQUIRE(layout == KVQ_GEMM_TN, "%s: layout TN only", who);
+    // the 256 x 256 problems first (their tiles are the launch's first, see gemm2_mixed_kernel), each class in the caller's order
+    kvq_gemm_problem sorted[g2::MAX_PROBLEMS];
+    int nb = 0;
+    for (int i = 0; i < nprob; ++i) {
+        KVQ_REQUIRE(tiles[i] == KVQ_GEMM_TILE_256x256 || tiles[i] == KVQ_GEMM_TILE_128x256, "%s: problem %d: tile must be 256x256 or 128x256", who, i);
+        if (tiles[i] == KVQ_GEMM_TILE_256x256) sorted[nb++] = probs[i];
+    }
+    int ns = nb;
+    for (int i = 0; i < nprob; ++i)
+        if (tiles[i] == KVQ_GEMM_TILE_128x256) sorted[ns++] = probs[i];
+    g2::Params P, S;
+    P.ntiles = 0;
+    if (nb)
+        if (int rc = build_params(sorted, nb, layout, KVQ_GEMM_TILE_256x256, P, who)) return rc;
+    const int nbig = P.ntiles;
+    if (nprob > nb) {
+        if (int rc = build_params(sorted + nb, nprob - nb, layout, KVQ_GEMM_TILE_128x256, S, who)) return rc;
+        for (int i = nb; i < nprob; ++i) {
+            P.p[i] = S.p[i - nb];
+            P.p[i].tile0 += nbig;
+        }
+        for (int i = nprob; i < g2::MAX_PROBLEMS; ++i) P.p[i] = P.p[0];
+        P.ntiles = nbig + S.ntiles;
+    }
+    P.nprob = nprob;
+    typedef g2::Cfg256x256<false, false> CA;
+    typedef g2::Cfg128x256<false, false> CB;
+    constexpr int LDS = CA::LDS > CB::LDS ? CA::LDS : CB::LDS;
+    static std::atomic<bool> attr_done{false};
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&g2::gemm2_mixed_kernel<CA, CB>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        if (e != hipSuccess) return fail(KVQ_E_LAUNCH, "hipFuncSetAttribute(gemm2_mixed): %s", hipGetErrorString(e));
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((g2::gemm2_mixed_kernel<CA, CB>), dim3((unsigned)P.ntiles), dim3(CA::THREADS), LDS, (hipStream_t)stream, P, nbig);
+    return check_launch("gemm2_mixed_kernel");
 }
 
 int kvq_gemm_bf16(const void* A, const void* B, const void* bias, void* C, int M, int N, int K, int lda, int ldb, int ldc,

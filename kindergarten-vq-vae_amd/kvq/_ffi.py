@@ -102,6 +102,7 @@ SIGNATURES = {
     "kvq_gemm_bf16": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _int, _vp]),
     "kvq_gemm_any_bf16": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _vp]),
     "kvq_gemm_grouped_bf16": (_int, [C.POINTER(GemmProblem), _int, _int, _int, _vp]),
+    "kvq_gemm_grouped_mixed_bf16": (_int, [C.POINTER(GemmProblem), C.POINTER(_int), _int, _int, _vp]),
     "kvq_fp8_quantize": (_int, [_vp, _i64, _int, _i64, _vp, _vp, _vp, _vp]),
     "kvq_fp8_state_floats": (_int, []),
     "kvq_fp8_quantize_delayed": (_int, [_vp, _i64, _int, _i64, _vp, _vp, _vp]),

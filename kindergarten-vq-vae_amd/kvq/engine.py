@@ -474,7 +474,9 @@ class TrainEngine:
         # weight gradients as grouped launches of csrc/kvq_gemm2.hip, two layers per launch where they fit one round of the CUs
         # (_flush_wgrads)
         self._own_wgrad = self._own_fwd and self.dtype == torch.bfloat16
-        self._wg_items, self._wg_keep = [], []
+        self._wg_pack = False                 # the packed schedule (one process only): set below, once _dp is known
+        self._n_cu = nnops.cu_count(dev)
+        self._wg_reset()
         # LM head + the loss' forward statistics in one kernel (see _forward_backward): built and parity-tested in round 2, and
         # 0.08 ms/step SLOWER than library GEMM + kvq_ce_forward (18.55 against 18.47 ms, gpurun_out/ab16.log): opt-in
         self._own_lmce = os.environ.get("KVQ_OWN_LMCE", "0") == "1"
@@ -485,6 +487,9 @@ class TrainEngine:
         # with a ONE-rank process group and KVQ_DP_SINGLE_RANK=1 (every all-reduce, stream hand-over and graph interlude executes;
         # the averages are over one rank)
         self._dp = self.world > 1 or (dist.is_initialized() and os.environ.get("KVQ_DP_SINGLE_RANK", "0") == "1")
+        # KVQ_WG_PACK=0: the unpacked weight-gradient schedule (A/B switch); with a process group always -- _wg_done_lo is one
+        # watermark that takes gradients to become final in buffer order, which the packed schedule's late cross-K/V slices are not
+        self._wg_pack = self._own_wgrad and not self._dp and os.environ.get("KVQ_WG_PACK", "1") != "0"
 
         # ---- flat parameter layout, in FORWARD order (gradients then complete from the tail backwards)
         entries, seen = [], set()
@@ -995,13 +1000,13 @@ class TrainEngine:
             return self._linear_fp8(x, W, b, key)
         return self._gemm(x, W, "nt", bias=b)
 
-    def _gemm(self, a, b, layout, bias=None, out=None, accumulate=False):
+    def _gemm(self, a, b, layout, bias=None, out=None, accumulate=False, tile=None):
         """op(a) . op(b) (+ bias) (accumulated into out).  bf16: libkvq.so, always (nnops.gemm: MFMA kernel or the any-shape one).
         f32 (the checker engine) and KVQ_OWN_GEMM=0 (A/B against the vendor library): torch."""
         if self._own_fwd and self.dtype == torch.bfloat16:
             M, N, K = nnops._gemm_dims(a, b, layout)
             wshape = (N, K) if layout == "nt" else ((K, N) if layout == "nn" else (M, N))
-            return nnops.gemm(a, b, layout, bias=bias, out=out, accumulate=accumulate, tile=self._TILE_OVERRIDE.get(wshape))
+            return nnops.gemm(a, b, layout, bias=bias, out=out, accumulate=accumulate, tile=self._TILE_OVERRIDE.get(wshape, tile))
         A = a.t() if layout == "tn" else a
         Bm = b.t() if layout == "nt" else b
         if out is not None and accumulate:
@@ -1074,26 +1079,86 @@ class TrainEngine:
 
     _WG_MAX = 16                                          # problems per grouped launch (csrc/kvq_gemm2.hip MAX_PROBLEMS)
 
+    # ------------------------------------------------------------------------------------------------------------
+    # weight-gradient queue.  A 256 x 256 TN tile over the whole token contraction keeps its CU for ~195 us whatever runs
+    # beside it, so a launch of up to one tile per CU costs one round of 210 - 225 us whether it holds 135, 216 or 255 tiles:
+    # the queue exists to make every round a full one.
+    #   * layers are held until two are there (_flush_wgrads): 216 (encoder) / 252 (decoder) tiles of 256 x 256;
+    #   * packed schedule (_wg_pack: one process, KVQ_WG_PACK != 0) --
+    #       - an output of between one and two rounds (the LM head, [30528, 768]) is one launch on two tile shapes
+    #         (nnops.gemm tile "mixed": the rows that fill the CUs once on 256 x 256 tiles, the rest on 128 x 256 tiles);
+    #       - weight gradients that belong to no layer pair are not queued but WAIT (_wgrad_fill) for the CUs a grouped
+    #         launch leaves idle, and are taken in whole units of rows: head.t.w in 256-row slices (3 tiles; a decoder pair
+    #         leaves 4 CUs), the all-layer cross-K/V gradient in per-layer slices (18 tiles; an encoder pair leaves 40).
+    #         So head.t.w never breaks the pairing -- (11, 10) .. (1, 0) in both stacks -- and cross-K/V has no round of its own;
+    #     everything is derived from tile counts and the CU count: what does not fit (other widths, frozen stacks, fewer
+    #     layers) is launched as before, and what nothing took goes out with the forced flush that ends backward;
+    #   * with a process group the schedule is the unpacked one, exactly: _wg_done_lo takes gradients to become final in
+    #     buffer order.
+    # Each output element comes from the same tile code, k order and accumulation in either schedule: bit-identical.
+    # ------------------------------------------------------------------------------------------------------------
+    def _wg_reset(self):
+        self._wg_items, self._wg_keep = [], []
+        self._wg_fill = []                    # packed: [gy, x, out, unit rows, next row] waiting for launches with idle CUs
+
     @staticmethod
     def _wg_tiles(items, bm, bn):
         return sum(-(-p.M // bm) * -(-p.N // bn) for p in items)
+
+    def _wgrad_fill(self, gy, x, out, unit):
+        """Packed schedule: gW = gy^T x without a launch of its own -- grouped launches that leave CUs idle take it in
+        pieces of whole `unit` rows (a multiple of 256: whole tile rows); gy and x stay alive until the last piece is taken.
+        Otherwise _wgrad."""
+        if self._wg_pack and unit % 256 == 0 and out.shape[0] % unit == 0 and gy.shape[0] % 64 == 0 \
+                and nnops.gemm_mfma_ok(gy, x, out, "tn"):
+            self._wg_fill.append([gy, x, out, unit, 0])
+            return
+        self._wgrad(gy, x, out)
+
+    def _take_fill(self, idle, bm, room):
+        """At most `room` problems whose bm x 256 tiles fit `idle` CUs: the largest units first, the small ones fill the gaps."""
+        taken = []
+        for f in sorted(self._wg_fill, key=lambda f: -(-(-f[3] // bm) * -(-f[2].shape[1] // 256))):
+            gy, x, out, unit, r0 = f
+            per_unit = -(-unit // bm) * -(-out.shape[1] // 256)
+            k = min(idle // per_unit, (out.shape[0] - r0) // unit) if len(taken) < room else 0
+            if k > 0:
+                r1 = r0 + k * unit
+                taken.append(nnops.gemm_problem(gy[:, r0:r1], x, out[r0:r1], "tn"))
+                f[4], idle = r1, idle - k * per_unit
+        self._wg_fill = [f for f in self._wg_fill if f[4] < f[2].shape[0]]
+        return taken
+
+    def _launch_group(self, items, fill=True):
+        """items as grouped launches on the tile their count asks for; a launch with idle CUs takes waiting weight gradients."""
+        t256 = self._wg_tiles(items, 256, 256)
+        tile = "256x256" if self._wg_tiles(items, 128, 256) > 256 and t256 <= 320 else "128x256"
+        if fill and self._wg_fill and len(items) < self._WG_MAX:
+            bm = 256 if tile == "256x256" else 128
+            items = items + self._take_fill(self._n_cu - self._wg_tiles(items, bm, 256), bm, self._WG_MAX - len(items))
+        for i in range(0, len(items), self._WG_MAX):
+            nnops.gemm_grouped(items[i:i + self._WG_MAX], "tn", tile)
 
     def _flush_wgrads(self, force=True):
         """The weight gradients queued so far as grouped launches, written straight into the flat bf16 gradient buffer, each
         tile contracting over all tokens (no split-K).  The kernel's rate is set by bytes staged per flop (the L2 -> LDS fill
         is the limit), so the 256 x 256 tile is the fast one -- but one BERT layer is only 108-126 of them.  The
         queue is therefore held (force=False) until TWO layers' worth is there: 216-252 tiles = one round of the 256 CUs.
-        Returns True when nothing is left queued."""
+        Packed schedule: the launch takes waiting weight gradients up to the CU count, and a forced flush launches what
+        nothing took, a round at a time.  Returns True when no layer is left queued."""
         items = self._wg_items
-        if not items:
-            return True
-        t256 = self._wg_tiles(items, 256, 256)
-        if not force and len(items) <= self._WG_MAX // 2 and 2 * t256 <= 256:
-            return False                                   # another layer like this one still fits the same round
-        tile = "256x256" if self._wg_tiles(items, 128, 256) > 256 and t256 <= 320 else "128x256"
-        for i in range(0, len(items), self._WG_MAX):
-            nnops.gemm_grouped(items[i:i + self._WG_MAX], "tn", tile)
-        self._wg_items, self._wg_keep = [], []
+        if items:
+            t256 = self._wg_tiles(items, 256, 256)
+            if not force and len(items) <= self._WG_MAX // 2 and 2 * t256 <= 256:
+                return False                               # another layer like this one still fits the same round
+            self._launch_group(items)
+            self._wg_items, self._wg_keep = [], []
+        while force and self._wg_fill:
+            rest = self._take_fill(self._n_cu, 256, self._WG_MAX)
+            if not rest:                                   # (a unit larger than the chip: whole, as _wgrad would have queued it)
+                rest = [nnops.gemm_problem(gy[:, r0:], x, out[r0:], "tn") for gy, x, out, _, r0 in self._wg_fill]
+                self._wg_fill = []
+            self._launch_group(rest, fill=False)
         return True
 
     def _flush_reductions(self, force=True):
@@ -1142,22 +1207,28 @@ class TrainEngine:
                 gy, x = padded
         if self._own_wgrad and nnops.gemm_mfma_ok(gy, x, out, "tn"):
             if -(-M // 256) * -(-N // 256) >= 128:
-                self._gemm(gy, x, "tn", out=out)
+                # packed schedule: between one and two rounds of 256 x 256 tiles -> one full round of them + a shorter one of 128 x 256
+                mixed = self._wg_pack and nnops.mixed_split(M, N, self._n_cu) > 0
+                self._gemm(gy, x, "tn", out=out, tile="mixed" if mixed else None)
             else:
                 self._wg_items.append(nnops.gemm_problem(gy, x, out, "tn"))
                 self._wg_keep += [gy, x]                       # alive until the grouped launch
             return
         self._gemm(gy, x, "tn", out=out)
 
-    def _linear_bwd(self, gy, x, wnames, bnames, need_gx=True, gx_accum=None, bias_done=False):
-        """Weight / bias gradients straight into the flat gradient buffer; returns gx (or accumulates into gx_accum)."""
+    def _linear_bwd(self, gy, x, wnames, bnames, need_gx=True, gx_accum=None, bias_done=False, fill_unit=None):
+        """Weight / bias gradients straight into the flat gradient buffer; returns gx (or accumulates into gx_accum).
+        fill_unit: a layer outside the stacks -- its weight gradient waits for idle CUs (_wgrad_fill) in slices of that many rows."""
         fl = self.flat
         if len(wnames) == 1:
             W, gW, gb = fl.w(wnames[0]), fl.g(wnames[0]), fl.g(bnames[0])
         else:
             W, gW, gb = fl.fused(wnames, fl.shadow), fl.fused(wnames, fl.grad), fl.fused(bnames, fl.grad)
         if fl.trainable[wnames[0]]:
-            self._wgrad(gy, x, gW)
+            if fill_unit:
+                self._wgrad_fill(gy, x, gW, fill_unit)
+            else:
+                self._wgrad(gy, x, gW)
         if fl.trainable[bnames[0]] and not bias_done:     # bias_done: the LayerNorm backward kernel already produced it
             self._defer_colsum(gy, gb)
         if not need_gx and gx_accum is None:
@@ -1492,7 +1563,7 @@ class TrainEngine:
             raise KvqError("TrainEngine: defer_backward is a single-process, eager, forward-first call")
         self._site_ctr = 0
         self._red_items, self._red_keep = [], []
-        self._wg_items, self._wg_keep = [], []
+        self._wg_reset()
         pre = getattr(self, "_prepared", None) or {}            # this batch's (sorted ids, order) per side: _normalise_prepared()
         self._sorted = {"enc.emb.": pre.get("enc"), "dec.emb.": pre.get("dec") if dec_ids is not None else "enc.emb."}
         # dropout seeds of this engine's launches = _step_seed + device step count (grad_accum > 1: + device micro-step count)
@@ -1758,7 +1829,7 @@ class TrainEngine:
             raise KvqError("TrainEngine.backward_from: parameters changed since the forward (an optimiser step or an in-place write)")
         resume["done"] = True
         self._red_items, self._red_keep = [], []
-        self._wg_items, self._wg_keep = [], []
+        self._wg_reset()
         self._sorted = resume["sorted_ids"]
         self._g_vq_ext = (g_loss_vq.detach().to(torch.float32).reshape(()) if g_loss_vq is not None
                           else torch.zeros((), dtype=torch.float32, device=self.dev)) if self.has_vq else None
@@ -1969,10 +2040,10 @@ class TrainEngine:
         if tr["head.t.b"] and t.is_contiguous() and t.shape[1] % 8 == 0:
             g_t, pb = nnops.gelu_bwd_bias(t, g_ta, out=g_ta)
             self._defer(pb, fl.g("head.t.b"), pb.shape[0], pb.shape[1], pb.shape[1])
-            g_y = self._linear_bwd(g_t, y, ["head.t.w"], ["head.t.b"], bias_done=True)
+            g_y = self._linear_bwd(g_t, y, ["head.t.w"], ["head.t.b"], bias_done=True, fill_unit=256)
         else:
             g_t = nnops.gelu_bwd(t, g_ta, out=g_ta)
-            g_y = self._linear_bwd(g_t, y, ["head.t.w"], ["head.t.b"])
+            g_y = self._linear_bwd(g_t, y, ["head.t.w"], ["head.t.b"], fill_unit=256)
         self._grads_done_down_to("head.t.w")
         g_kv_all = pb_kv_all = None
         if self._cakv_batched:
@@ -1994,7 +2065,7 @@ class TrainEngine:
             dec_saved[i] = None
         if self._cakv_batched:             # all layers' key/value projections at once: weight, bias and input gradients
             if tr[self._cakv_w[0]]:
-                self._wgrad(g_kv_all, enc_out, fl.fused(self._cakv_w, fl.grad))
+                self._wgrad_fill(g_kv_all, enc_out, fl.fused(self._cakv_w, fl.grad), 2 * H)      # per-layer slices
             if pb_kv_all is not None:
                 self._defer(pb_kv_all, fl.fused(self._cakv_b, fl.grad), B, pb_kv_all.shape[1], pb_kv_all.shape[1])
             g_enc = self._dgrad(g_kv_all, fl.fused(self._cakv_w, fl.shadow), key=self._cakv_w[0])
@@ -2929,7 +3000,7 @@ class TrainEngine:
             self._pending_hi = self.flat.n
         self._wg_done_lo = self.flat.n
         self._red_items, self._red_keep = [], []
-        self._wg_items, self._wg_keep = [], []
+        self._wg_reset()
 
     def eval_step(self, input_ids, attention_mask, dec_ids=None, dec_mask=None, target_ids=None):
         return self.forward_backward(input_ids, attention_mask, training=False, compute_grads=False, dec_ids=dec_ids, dec_mask=dec_mask,

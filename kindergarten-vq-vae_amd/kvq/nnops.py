@@ -615,6 +615,19 @@ def persistent_pays(t, M, N, K, layout, accumulate=False, n_cu=256):
     return 3 <= per_cu <= 12
 
 
+def cu_count(device):
+    return torch.cuda.get_device_properties(device).multi_processor_count
+
+
+def mixed_split(M, N, n_cu):
+    """The row split of the "mixed" tile of an [M, N] weight gradient: r rows -- the most whole 256-row tile rows that fit n_cu CUs
+    once -- on 256 x 256 tiles and the other M - r on 128 x 256 tiles, when those fit the CUs once as well: one full round of the large
+    tile and a shorter one of the small tile instead of up to three of the small one.  0: the shape does not split that way."""
+    tn = -(-N // 256)
+    r = n_cu // tn * 256
+    return r if 0 < r < M and -(-(M - r) // 128) * tn <= n_cu else 0
+
+
 def gemm_mfma_ok(a, b, out, layout, bias=None):
     """True when kvq_gemm_bf16 (LDS-DMA + MFMA, csrc/kvq_gemm2.hip) takes this product: K % 64 == 0; M, N and the leading dimensions
     in multiples of 8; 16-byte aligned operands (bias: 8); unit column stride."""
@@ -695,7 +708,8 @@ def gemm(a, b, layout="nt", bias=None, out=None, accumulate=False, tile=None):
     from pick_tile() unless given.  Products that miss them only through their TOKEN count still reach it: a "tn" contraction
     over tokens is zero-padded to a multiple of 64 (tn_operands_k64), an "nt" / "nn" product over a token count that is not a
     multiple of 8 runs its first M - M % 8 rows there and the last rows on the any-shape kernel of csrc/kvq_gemm_any.hip, which
-    also takes everything else (with a warning above 64 MFLOP).  Never a vendor library."""
+    also takes everything else (with a warning above 64 MFLOP).  Never a vendor library.  tile "mixed" (plain "tn" products that
+    mixed_split() splits): one launch on two tile shapes, see there."""
     require_gpu(a, b)
     M, N, K = _gemm_dims(a, b, layout)
     if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or (out is not None and out.dtype != torch.bfloat16):
@@ -715,6 +729,17 @@ def gemm(a, b, layout="nt", bias=None, out=None, accumulate=False, tile=None):
             _gemm_any(a[M8:], b, layout, bias, out[M8:], accumulate, warn=False)                 # (at most 7 rows)
             return out
         return _gemm_any(a, b, layout, bias, out, accumulate)
+    if tile == "mixed":
+        # one product on two tile shapes (kvq_gemm_grouped_mixed_bf16), split by rows from the CU count
+        r = mixed_split(M, N, cu_count(a.device)) if layout == "tn" and bias is None and not accumulate else 0
+        if not r:
+            raise KvqError(f"kvq.nnops.gemm: tile 'mixed' is for plain tn products that mixed_split() splits (M={M} N={N} {layout})")
+        from ._ffi import GemmProblem
+        GEMM_ROUTES["mfma"] += 1
+        parts = [GemmProblem(a_.data_ptr(), b.data_ptr(), o_.data_ptr(), None, o_.shape[0], N, K, a.stride(0), b.stride(0), out.stride(0), 0)
+                 for a_, o_ in ((a[:, :r], out[:r]), (a[:, r:], out[r:]))]
+        gemm_grouped_mixed(parts, ["256x256", "128x256"], "tn")
+        return out
     if tile is None:
         t = pick_tile(M, N, K)
         if persistent_pays(t, M, N, K, layout, accumulate):
@@ -733,6 +758,18 @@ def gemm_grouped(problems, layout, tile):
     arr = (GemmProblem * len(problems))(*problems)
     t = TILES[tile] if isinstance(tile, str) else tile
     check(lib().kvq_gemm_grouped_bf16(arr, len(problems), _LAYOUTS[layout], t, stream_ptr()), "kvq_gemm_grouped_bf16")
+
+
+def gemm_grouped_mixed(problems, tiles, layout="tn"):
+    """One launch over a list of "tn" gemm_problem()s (at most 16), each on its own tile ("256x256" or "128x256"): the 256 x 256
+    tiles run first.  Bit for bit what gemm_grouped() stores for each problem on its tile."""
+    import ctypes
+    from ._ffi import GemmProblem
+    if len(tiles) != len(problems):
+        raise KvqError("kvq.nnops.gemm_grouped_mixed: one tile per problem")
+    arr = (GemmProblem * len(problems))(*problems)
+    ts = (ctypes.c_int * len(tiles))(*[TILES[t] if isinstance(t, str) else t for t in tiles])
+    check(lib().kvq_gemm_grouped_mixed_bf16(arr, ts, len(problems), _LAYOUTS[layout], stream_ptr()), "kvq_gemm_grouped_mixed_bf16")
 
 
 def gemm_gelu(x, w, bias, tile="256x192"):
