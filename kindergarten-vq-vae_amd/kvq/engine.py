@@ -561,7 +561,7 @@ class TrainEngine:
             raise KvqError("TrainEngine expects the same padding_idx in the encoder and decoder word embeddings")
         self._pad_idx = pads.pop()
         # option, off by default: reconstruction loss, accuracy and per-sentence accuracy over the tokens whose
-        # target is not the pad id (F.cross_entropy's ignore_index) -- the kvq_*_ignore twins of the loss kernels, one for one
+        # target is not the pad id (F.cross_entropy's ignore_index) -- the kvq_*_ignore entry points of the loss kernels
         if self.loss_ignore_pad and self._pad_idx is None:
             raise KvqError("TrainEngine: loss_ignore_pad (KVQ_LOSS_IGNORE_PAD) needs word embeddings with a padding_idx: there is no "
                            "pad id to leave out of the loss")
@@ -1966,22 +1966,12 @@ class TrainEngine:
             ce_out = torch.empty(2, dtype=torch.float32, device=self.dev)
         if lm_stats is not None:
             nnops.ce_forward_stats(logits, tgt, lm_stats, row_loss, row_lse, pred, ce_out[0:], ce_out[1:], ignore_index=ign, count=ce_cnt)
-        elif ign is not None:
-            check(lib().kvq_ce_forward_ignore(logits.data_ptr(), tgt.data_ptr(), Nd, self.V, self.Vp, self.io, ign, row_loss.data_ptr(),
-                                              row_lse.data_ptr(), pred.data_ptr(), ce_out[0:].data_ptr(), ce_out[1:].data_ptr(),
-                                              ce_cnt.data_ptr(), stream_ptr()), "kvq_ce_forward_ignore")
         else:
-            check(lib().kvq_ce_forward(logits.data_ptr(), tgt.data_ptr(), Nd, self.V, self.Vp, self.io, row_loss.data_ptr(),
-                                       row_lse.data_ptr(), pred.data_ptr(), ce_out[0:].data_ptr(), ce_out[1:].data_ptr(), stream_ptr()),
-                  "kvq_ce_forward")
+            nnops.ce_forward(logits, tgt, self.V, self.Vp, row_loss, row_lse, pred, ce_out[0:], ce_out[1:], ignore_index=ign, count=ce_cnt)
         acc_sent = None
         if self.sentence_acc or latents is not None:     # seq_acc's second result (common/metrics.py:32-36), read by the Bagon trainer's decode step
             acc_sent = torch.empty(B, dtype=torch.float32, device=self.dev)
-            if ign is not None:
-                check(lib().kvq_seq_acc_ignore(pred.data_ptr(), tgt.data_ptr(), B, Sd, ign, acc_sent.data_ptr(), stream_ptr()),
-                      "kvq_seq_acc_ignore")
-            else:
-                check(lib().kvq_seq_acc(pred.data_ptr(), tgt.data_ptr(), B, Sd, acc_sent.data_ptr(), stream_ptr()), "kvq_seq_acc")
+            nnops.seq_acc(pred, tgt, B, Sd, acc_sent, ignore_index=ign)
         out = dict(loss_recon=ce_out[0] if self.w_recon == 1.0 else ce_out[0] * self.w_recon,
                    loss_vq=(loss_vq if self.w_vq == 1.0 else loss_vq * self.w_vq) if loss_vq is not None else None,
                    perplexity=perplexity, acc=ce_out[1], acc_per_sentence=acc_sent, recon_ids=pred.view(B, Sd), indices=indices)
@@ -2008,25 +1998,13 @@ class TrainEngine:
                 self._defer_colsum(g_logits, fl.g("head.bias", rows=self.Vp))
         elif tr["head.bias"] and self.Vp % 8 == 0:
             # in place: logits := d loss / d logits; the LM-head bias gradient leaves the same pass as partial column sums
-            pb = torch.empty((lib().kvq_ce_bwd_partial_rows(Nd), self.Vp), dtype=torch.float32, device=self.dev)
-            if ign is not None:         # the count is read from the slot the forward's finalize wrote, on the device
-                check(lib().kvq_ce_backward_bias_ignore(logits.data_ptr(), tgt.data_ptr(), row_lse.data_ptr(), g_scale.data_ptr(),
-                                                        ce_cnt.data_ptr(), ign, Nd, self.V, self.Vp, self.io, logits.data_ptr(),
-                                                        pb.data_ptr(), pb.numel() * 4, stream_ptr()), "kvq_ce_backward_bias_ignore")
-            else:
-                check(lib().kvq_ce_backward_bias(logits.data_ptr(), tgt.data_ptr(), row_lse.data_ptr(), g_scale.data_ptr(), Nd, self.V,
-                                                 self.Vp, self.io, logits.data_ptr(), pb.data_ptr(), pb.numel() * 4, stream_ptr()),
-                      "kvq_ce_backward_bias")
+            pb = torch.empty((nnops.ce_bwd_partial_rows(Nd), self.Vp), dtype=torch.float32, device=self.dev)
+            # (with ign the count is read from the slot the forward's finalize wrote, on the device)
+            nnops.ce_backward_bias(logits, tgt, row_lse, g_scale, self.V, self.Vp, logits, pb, ignore_index=ign, count=ce_cnt)
             self._defer(pb, fl.g("head.bias", rows=self.Vp), pb.shape[0], self.Vp, self.Vp)
             g_logits = logits
         else:
-            if ign is not None:
-                check(lib().kvq_ce_backward_ignore(logits.data_ptr(), tgt.data_ptr(), row_lse.data_ptr(), g_scale.data_ptr(),
-                                                   ce_cnt.data_ptr(), ign, Nd, self.V, self.Vp, self.io, logits.data_ptr(),
-                                                   stream_ptr()), "kvq_ce_backward_ignore")                # in place
-            else:
-                check(lib().kvq_ce_backward(logits.data_ptr(), tgt.data_ptr(), row_lse.data_ptr(), g_scale.data_ptr(), Nd, self.V, self.Vp,
-                                            self.io, logits.data_ptr(), stream_ptr()), "kvq_ce_backward")      # in place
+            nnops.ce_backward(logits, tgt, row_lse, g_scale, self.V, self.Vp, logits, ignore_index=ign, count=ce_cnt)      # in place
             g_logits = logits
             if tr["head.bias"]:
                 self._defer_colsum(g_logits, fl.g("head.bias", rows=self.Vp))

@@ -359,6 +359,7 @@ class _FusedCE(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, target, inplace_backward, ignore_index=None):
+        from . import nnops               # (nnops imports this module)
         require_gpu(logits, target)
         if not logits.is_contiguous():
             raise _ffi.KvqError("fused_cross_entropy: logits must be contiguous")
@@ -369,17 +370,10 @@ class _FusedCE(torch.autograd.Function):
         row_lse = torch.empty(N, dtype=torch.float32, device=dev)
         pred = torch.empty(N, dtype=torch.int64, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)
-        if ignore_index is None:
-            check(lib().kvq_ce_forward(logits.data_ptr(), target.data_ptr(), N, V, V, io_dtype_of(logits), row_loss.data_ptr(),
-                                       row_lse.data_ptr(), pred.data_ptr(), out[0:].data_ptr(), out[1:].data_ptr(),
-                                       stream_ptr()), "kvq_ce_forward")
-            ctx.save_for_backward(logits, target, row_lse)
-        else:
-            check(lib().kvq_ce_forward_ignore(logits.data_ptr(), target.data_ptr(), N, V, V, io_dtype_of(logits), int(ignore_index),
-                                              row_loss.data_ptr(), row_lse.data_ptr(), pred.data_ptr(), out[0:].data_ptr(),
-                                              out[1:].data_ptr(), out[2:].data_ptr(), stream_ptr()), "kvq_ce_forward_ignore")
-            ctx.save_for_backward(logits, target, row_lse, out[2:])
         ctx.ignore_index = None if ignore_index is None else int(ignore_index)
+        count = None if ignore_index is None else out[2:]                 # the number of counted rows stays on the device
+        nnops.ce_forward(logits, target, V, V, row_loss, row_lse, pred, out[0:], out[1:], ignore_index=ctx.ignore_index, count=count)
+        ctx.save_for_backward(logits, target, row_lse, count)
         ctx.inplace = bool(inplace_backward)
         loss, acc = out[0], out[1]
         ctx.mark_non_differentiable(acc, pred)
@@ -387,18 +381,12 @@ class _FusedCE(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, _ga, _gp):
-        logits, target, row_lse = ctx.saved_tensors[:3]
+        from . import nnops
+        logits, target, row_lse, count = ctx.saved_tensors
         N, V = logits.shape
         g = logits if ctx.inplace else torch.empty_like(logits)
         g_loss = g_loss.contiguous().float()
-        if ctx.ignore_index is None:
-            check(lib().kvq_ce_backward(logits.data_ptr(), target.data_ptr(), row_lse.data_ptr(), g_loss.data_ptr(), N, V, V,
-                                        io_dtype_of(logits), g.data_ptr(), stream_ptr()), "kvq_ce_backward")
-        else:
-            count = ctx.saved_tensors[3]
-            check(lib().kvq_ce_backward_ignore(logits.data_ptr(), target.data_ptr(), row_lse.data_ptr(), g_loss.data_ptr(),
-                                               count.data_ptr(), ctx.ignore_index, N, V, V, io_dtype_of(logits), g.data_ptr(),
-                                               stream_ptr()), "kvq_ce_backward_ignore")
+        nnops.ce_backward(logits, target, row_lse, g_loss, V, V, g, ignore_index=ctx.ignore_index, count=count)
         return g, None, None, None
 
 

@@ -832,19 +832,95 @@ def gemm_ce(x, w, bias, V):
     return logits, stats
 
 
-def ce_forward_stats(logits, target, stats, row_loss, row_lse, pred, loss, acc, ignore_index=None, count=None):
-    """kvq_ce_forward's outputs from gemm_ce()'s statistics (reads one logit per row).  ignore_index: the means run over the rows
-    whose target differs from it, and `count` [1] f32 receives their number (kvq_ce_forward_stats_ignore)."""
+# ---- the reconstruction loss (csrc/kvq_ce.hip).  Every pass has two entry points, kvq_X and kvq_X_ignore; these wrappers pick one:
+# ignore_index=None is kvq_X, an int is kvq_X_ignore, whose means run over the rows whose target differs from it.  `count` [1] f32 on
+# the device is their number: the forward passes write it (optional there), the backward passes read it (required).  No allocation
+# and no synchronisation: the engine calls these while a step is being captured.
+def _ce_ignore(who, ignore_index, count, count_required=False):
+    """ignore_index as the int the _ignore entry point takes, or None for the entry point without it."""
+    if ignore_index is None:
+        if count is not None:
+            raise KvqError(f"{who}: count is only used together with an ignore_index")
+        return None
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, int):
+        raise KvqError(f"{who}: ignore_index must be None or an int, got {ignore_index!r}")
+    if count is None and count_required:
+        raise KvqError(f"{who}: ignore_index={ignore_index} needs the count the forward pass wrote")
+    return ignore_index
+
+
+def ce_forward(logits, target, V, ld, row_loss, row_lse, pred, loss, acc, ignore_index=None, count=None):
+    """Rows of V logits at stride ld -> row_loss, row_lse, pred [N] and the means loss, acc [1] (kvq_ce_forward / _ignore)."""
+    ign = _ce_ignore("ce_forward", ignore_index, count)
     N = logits.shape[0]
-    if ignore_index is not None:
+    if ign is None:
+        check(lib().kvq_ce_forward(logits.data_ptr(), target.data_ptr(), N, V, ld, io_dtype_of(logits), row_loss.data_ptr(),
+                                   row_lse.data_ptr(), pred.data_ptr(), _p(loss), _p(acc), stream_ptr()), "kvq_ce_forward")
+    else:
+        check(lib().kvq_ce_forward_ignore(logits.data_ptr(), target.data_ptr(), N, V, ld, io_dtype_of(logits), ign, row_loss.data_ptr(),
+                                          row_lse.data_ptr(), pred.data_ptr(), _p(loss), _p(acc), _p(count), stream_ptr()),
+              "kvq_ce_forward_ignore")
+
+
+def ce_forward_stats(logits, target, stats, row_loss, row_lse, pred, loss, acc, ignore_index=None, count=None):
+    """ce_forward's outputs from gemm_ce()'s statistics (reads one logit per row; kvq_ce_forward_stats / _ignore)."""
+    ign = _ce_ignore("ce_forward_stats", ignore_index, count)
+    N = logits.shape[0]
+    if ign is None:
+        check(lib().kvq_ce_forward_stats(logits.data_ptr(), target.data_ptr(), N, logits.stride(0), io_dtype_of(logits), stats.data_ptr(),
+                                         stats.shape[1], row_loss.data_ptr(), row_lse.data_ptr(), pred.data_ptr(), _p(loss), _p(acc),
+                                         stream_ptr()), "kvq_ce_forward_stats")
+    else:
         check(lib().kvq_ce_forward_stats_ignore(logits.data_ptr(), target.data_ptr(), N, logits.stride(0), io_dtype_of(logits),
-                                                stats.data_ptr(), stats.shape[1], int(ignore_index), row_loss.data_ptr(),
-                                                row_lse.data_ptr(), pred.data_ptr(), _p(loss), _p(acc), _p(count), stream_ptr()),
+                                                stats.data_ptr(), stats.shape[1], ign, row_loss.data_ptr(), row_lse.data_ptr(),
+                                                pred.data_ptr(), _p(loss), _p(acc), _p(count), stream_ptr()),
               "kvq_ce_forward_stats_ignore")
-        return
-    check(lib().kvq_ce_forward_stats(logits.data_ptr(), target.data_ptr(), N, logits.stride(0), io_dtype_of(logits), stats.data_ptr(),
-                                     stats.shape[1], row_loss.data_ptr(), row_lse.data_ptr(), pred.data_ptr(), _p(loss), _p(acc),
-                                     stream_ptr()), "kvq_ce_forward_stats")
+
+
+def seq_acc(pred, target, B, S, per_sentence, ignore_index=None):
+    """per_sentence [B] = the share of each sentence's S (counted) tokens with pred == target (kvq_seq_acc / _ignore)."""
+    ign = _ce_ignore("seq_acc", ignore_index, None)
+    if pred.numel() != B * S or target.numel() != B * S or per_sentence.numel() != B:
+        raise KvqError(f"seq_acc: pred and target must hold {B} * {S} ids and per_sentence {B} values, got {pred.numel()}, "
+                       f"{target.numel()} and {per_sentence.numel()}")
+    if ign is None:
+        check(lib().kvq_seq_acc(pred.data_ptr(), target.data_ptr(), B, S, per_sentence.data_ptr(), stream_ptr()), "kvq_seq_acc")
+    else:
+        check(lib().kvq_seq_acc_ignore(pred.data_ptr(), target.data_ptr(), B, S, ign, per_sentence.data_ptr(), stream_ptr()),
+              "kvq_seq_acc_ignore")
+
+
+def ce_backward(logits, target, row_lse, g_loss, V, ld, out, ignore_index=None, count=None):
+    """out := g_loss * d mean(row_loss) / d logits, padding columns [V, ld) zero; out may be logits (kvq_ce_backward / _ignore).
+    g_loss: [1] f32 on the device, or None for 1."""
+    ign = _ce_ignore("ce_backward", ignore_index, count, count_required=True)
+    N = logits.shape[0]
+    if ign is None:
+        check(lib().kvq_ce_backward(logits.data_ptr(), target.data_ptr(), row_lse.data_ptr(), _p(g_loss), N, V, ld, io_dtype_of(logits),
+                                    out.data_ptr(), stream_ptr()), "kvq_ce_backward")
+    else:
+        check(lib().kvq_ce_backward_ignore(logits.data_ptr(), target.data_ptr(), row_lse.data_ptr(), _p(g_loss), count.data_ptr(), ign,
+                                           N, V, ld, io_dtype_of(logits), out.data_ptr(), stream_ptr()), "kvq_ce_backward_ignore")
+
+
+def ce_bwd_partial_rows(N):
+    """Rows of ce_backward_bias's bias_part for N rows of logits: one per block of rows of the tiled kernel."""
+    return lib().kvq_ce_bwd_partial_rows(N)
+
+
+def ce_backward_bias(logits, target, row_lse, g_loss, V, ld, out, bias_part, ignore_index=None, count=None):
+    """ce_backward with 16-byte aligned rows, which also leaves the column sums of out per block of rows in bias_part
+    [kvq_ce_bwd_partial_rows(N), ld] f32 (kvq_ce_backward_bias / _ignore)."""
+    ign = _ce_ignore("ce_backward_bias", ignore_index, count, count_required=True)
+    N = logits.shape[0]
+    if ign is None:
+        check(lib().kvq_ce_backward_bias(logits.data_ptr(), target.data_ptr(), row_lse.data_ptr(), _p(g_loss), N, V, ld,
+                                         io_dtype_of(logits), out.data_ptr(), bias_part.data_ptr(), bias_part.numel() * 4, stream_ptr()),
+              "kvq_ce_backward_bias")
+    else:
+        check(lib().kvq_ce_backward_bias_ignore(logits.data_ptr(), target.data_ptr(), row_lse.data_ptr(), _p(g_loss), count.data_ptr(), ign,
+                                                N, V, ld, io_dtype_of(logits), out.data_ptr(), bias_part.data_ptr(),
+                                                bias_part.numel() * 4, stream_ptr()), "kvq_ce_backward_bias_ignore")
 
 
 FP8_FORMATS = {"e4m3": FP8_E4M3, "e5m2": FP8_E5M2, FP8_E4M3: FP8_E4M3, FP8_E5M2: FP8_E5M2}

@@ -155,3 +155,41 @@ def test_entry_points_refuse_before_any_launch():
     assert b"null pointer" in lib.kvq_last_error()
     assert lib.kvq_ce_backward_bias_ignore(one, one, one, None, None, 0, 9, 8, 8, 0, one, one, 1 << 20, None) != 0
     assert lib.kvq_seq_acc_ignore(None, one, 5, 12, 0, one, None) != 0
+
+
+# ---- the nnops wrappers that pick the entry point -----------------------------------------------------------------------------------
+class _NoLibrary:
+    def __getattr__(self, name):
+        raise AssertionError(f"the library was reached ({name}) before the arguments were checked")
+
+
+def test_loss_wrappers_check_ignore_index_and_count_before_the_library(monkeypatch):
+    """ignore_index and count go together: a count without an ignore_index is refused by every wrapper that takes one, an
+    ignore_index without a count by the backward ones (their entry points read it), and an ignore_index that is no int by all --
+    on CPU tensors, with the library out of reach."""
+    from kvq import nnops
+    from kvq._ffi import KvqError
+    monkeypatch.setattr(nnops, "lib", lambda: _NoLibrary())
+    N, V = 4, 8
+    x = torch.zeros(N, V); t = torch.zeros(N, dtype=torch.int64); f = torch.zeros(N); p = torch.zeros(N, dtype=torch.int64)
+    s = torch.zeros(1); part = torch.zeros(1, V); stats = torch.zeros(N, 1, 4)
+    calls = {
+        "ce_forward": lambda **kw: nnops.ce_forward(x, t, V, V, f, f, p, s, s, **kw),
+        "ce_forward_stats": lambda **kw: nnops.ce_forward_stats(x, t, stats, f, f, p, s, s, **kw),
+        "ce_backward": lambda **kw: nnops.ce_backward(x, t, f, s, V, V, x, **kw),
+        "ce_backward_bias": lambda **kw: nnops.ce_backward_bias(x, t, f, s, V, V, x, part, **kw),
+    }
+    for name, call in calls.items():
+        with pytest.raises(KvqError, match=name + ": count"):
+            call(ignore_index=None, count=s)
+        for bad in (True, 0.0, "0", s):
+            with pytest.raises(KvqError, match=name + ": ignore_index must be"):
+                call(ignore_index=bad, count=s)
+    for name in ("ce_backward", "ce_backward_bias"):
+        with pytest.raises(KvqError, match=name + ": ignore_index=-100 needs the count"):
+            calls[name](ignore_index=-100, count=None)
+    with pytest.raises(KvqError, match="seq_acc: ignore_index must be"):
+        nnops.seq_acc(p, t, 2, 2, torch.zeros(2), ignore_index=False)
+    for args in ((p, t, 2, 3, torch.zeros(2)), (p, t[:3], 2, 2, torch.zeros(2)), (p, t, 2, 2, torch.zeros(3))):
+        with pytest.raises(KvqError, match="seq_acc: pred and target must hold"):
+            nnops.seq_acc(*args, ignore_index=0)
