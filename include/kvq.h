@@ -598,6 +598,46 @@ int kvq_adam_step_guarded_fp8(float* p, const void* g, float* m, float* v, float
                               void* w8_mirror, const int* span_segment, const float* seg_scale, const int64_t* seg_off,
                               const int64_t* seg_n, int nseg, int64_t first_element, const void* guard, void* stream);
 
+/* ---- parameter groups, decoupled weight decay and a learning-rate schedule in the step (csrc/kvq_nn.hip) ------------------------
+ * Extension, off by default (TrainEngine(param_groups=..., decoupled_weight_decay=..., lr_warmup_steps=..., lr_decay=...)).
+ * kvq_adam_step_grouped[_guarded]  kvq_adam_step_dev [kvq_adam_step_guarded] with a learning-rate scale s_j and a weight decay wd_j
+ *                          per parameter GROUP j, looked up inside the one launch.  block_group[(first_element + e) >> 4] names
+ *                          the group (0 .. n_groups - 1) of element e of the launch: one byte per 16-element block of the FLAT buffer
+ *                          the range [first_element, first_element + n) was cut from (first_element a multiple of 16; the engine
+ *                          starts and pads every parameter at multiples of 16, so a block never straddles two parameters).  Only the
+ *                          bytes of the launch's own blocks are read.  A byte is NOT validated: the kernel uses its low four bits (so
+ *                          no table byte can index outside its 16 table slots) and slots >= n_groups hold scale 0, decay 0 -- a
+ *                          corrupt table trains silently under a wrong or a zero rate; building it right is the caller's job
+ *                          (kvq.engine.param_group_blocks).  block_group == NULL: one group for the whole launch, entry 0
+ *                          of the two tables (the aux parameters, a range inside one group): the work of kvq_adam_step_dev.
+ *                          group_lr_scale / group_wd: n_groups (1 .. 16) floats of device memory each; NULL = every scale 1 /
+ *                          every decay `weight_decay`.  Per element of group j, with lr, bc1, bc2s from the step state and the
+ *                          gradient scaled by grad_scale [* guard->coef] as in kvq_adam_step_dev:  lr_j = fl(lr * s_j);
+ *                            decoupled = 0  the statements of kvq_adam_step_dev with wd_j for weight_decay and lr_j for lr;
+ *                            decoupled = 1  torch.optim.AdamW: p0 = fl(p * fl(1 - fl(lr_j * wd_j))), the moments from the scaled
+ *                                           gradient alone, p' = fl(p0 - u) with kvq_adam_step_dev's u.
+ *                          s_j = 0 does not freeze a group: its moments still move (and, decoupled = 0, see its weight decay).
+ *                          Every s_j = 1, every wd_j = weight_decay, decoupled = 0: the bits of kvq_adam_step_dev / _guarded.
+ *                          With guard->skip set nothing is stored.  There is no grouped form of the fp8-mirror entries.
+ * kvq_step_state_advance_sched  kvq_step_state_advance with a warm-up and a decay: for the 1-based step t being applied
+ *                            lr(t) = lr0 * gamma^k * warm * dec      (k as in kvq_step_state_advance; in double, rounded to f32 once)
+ *                            warm  = t / W while t < W (W = warmup_steps > 0), else 1
+ *                            x     = clamp((t - W) / (T - W), 0, 1)   (T = total_steps > W, required when decay_kind != 0)
+ *                            dec   = 1 (decay_kind 0), 1 - (1 - r) x (1, linear), r + (1 - r) (1 + cos(pi x)) / 2 (2, cosine),
+ *                                    r = min_ratio in [0, 1]
+ *                          Past T the rate STAYS at r * lr0 * gamma^k: it does not climb again as torch's CosineAnnealingLR does.
+ *                          warmup_steps = 0 and decay_kind = 0: the bits of kvq_step_state_advance.  The 24-byte state is unchanged. */
+int kvq_adam_step_grouped(float* p, const void* g, float* m, float* v, float* vmax, void* shadow_bf16, int64_t n, int grad_dtype,
+                          const void* step_state, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                          const uint8_t* block_group, int64_t first_element, const float* group_lr_scale, const float* group_wd,
+                          int n_groups, int decoupled, void* stream);
+int kvq_adam_step_grouped_guarded(float* p, const void* g, float* m, float* v, float* vmax, void* shadow_bf16, int64_t n, int grad_dtype,
+                                  const void* step_state, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                  const uint8_t* block_group, int64_t first_element, const float* group_lr_scale, const float* group_wd,
+                                  int n_groups, int decoupled, const void* guard, void* stream);
+int kvq_step_state_advance_sched(void* step_state, float lr0, float gamma, const int64_t* milestones, int n_milestones, float beta1,
+                                 float beta2, int64_t warmup_steps, int decay_kind, int64_t total_steps, float min_ratio, void* stream);
+
 /* ---- gradient accumulation over the micro-batches of one optimiser step (csrc/kvq_accum.hip) ----------------------------------
  * Extension, off by default (TrainEngine(grad_accum=A)): forward and backward run A times, Adam once, on the MEAN of the A
  * gradients -- (loss / A).backward() A times, then opt.step().  The flat gradient is bf16 and rewritten by every backward, so the sum

@@ -141,6 +141,11 @@ SIGNATURES = {
     "kvq_adam_step_guarded": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "kvq_adam_step_guarded_fp8": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp,
                                          _int, _i64, _vp, _vp]),
+    "kvq_adam_step_grouped": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _i64, _vp, _vp, _int,
+                                     _int, _vp]),
+    "kvq_adam_step_grouped_guarded": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _i64, _vp, _vp,
+                                             _int, _int, _vp, _vp]),
+    "kvq_step_state_advance_sched": (_int, [_vp, _f32, _f32, C.POINTER(_i64), _int, _f32, _f32, _i64, _int, _i64, _f32, _vp]),
     "kvq_vq_usage_flags": (_int, [_vp, _i64, _int, _int, _vp, _vp]),
     "kvq_vq_revive_select": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, C.c_uint64, _int, _int, _vp, _vp, _vp]),
     "kvq_vq_revive_apply": (_int, [_vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

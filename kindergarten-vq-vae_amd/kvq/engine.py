@@ -73,6 +73,66 @@ def fp8_span_table(offs, ns, n_total, span=2048):
     return table
 
 
+# ---- parameter groups and the learning-rate schedule: host side, plain Python / CPU tensors ---------------
+# The BERT fine-tuning recipe as one line of a config: {"match": NO_DECAY, "weight_decay": 0.0} -- biases, LayerNorm gains and the
+# LM-head bias take no weight decay.
+NO_DECAY = ["*.b", "*.ln.w", "*.ln2.w", "head.bias"]
+MAX_PARAM_GROUPS = 15          # beside group 0: kvq_adam_step_grouped holds 16 table entries
+
+
+def resolve_param_groups(spec, names, default_wd):
+    """spec: check_param_groups' list of {"match": [patterns], "lr_scale", "weight_decay" | None}; names: every parameter name of the
+    engine, in its order.  Returns (table, group_of): table[j] = dict(group, match, lr_scale, weight_decay, names) with group 0 =
+    what nothing matches (scale 1, default_wd), and group_of[name] = j.  First match wins (fnmatch, case-sensitive); a pattern that
+    matches no name at all is refused by name -- a typo must not silently train under the defaults."""
+    import fnmatch
+    table = [dict(group=0, match=[], lr_scale=1.0, weight_decay=float(default_wd), names=[])]
+    for j, g in enumerate(spec):
+        for pat in g["match"]:
+            if not any(fnmatch.fnmatchcase(n, pat) for n in names):
+                raise KvqError(f"TrainEngine: param_groups[{j}]: the pattern {pat!r} matches no parameter name (param_names() lists them)")
+        table.append(dict(group=j + 1, match=list(g["match"]), lr_scale=float(g["lr_scale"]),
+                          weight_decay=float(default_wd if g["weight_decay"] is None else g["weight_decay"]), names=[]))
+    group_of = {}
+    for n in names:
+        j = next((j + 1 for j, g in enumerate(spec) if any(fnmatch.fnmatchcase(n, pat) for pat in g["match"])), 0)
+        group_of[n] = j
+        table[j]["names"].append(n)
+    return table, group_of
+
+
+def param_group_blocks(layout, n_total, group_of):
+    """block_group of kvq_adam_step_grouped as a CPU uint8 tensor of n_total / 16 entries.  layout: [(name, first element)] in buffer
+    order, every first element and n_total a multiple of 16 (FlatParams); an entry owns the blocks up to the next entry's first one,
+    its alignment padding included."""
+    if n_total % 16 or any(o % 16 for _, o in layout):
+        raise KvqError("param_group_blocks: entries must start at multiples of 16 elements")
+    blocks = torch.zeros(n_total // 16, dtype=torch.uint8)
+    ends = [o for _, o in layout[1:]] + [n_total]
+    for (name, o), e in zip(layout, ends):
+        if e < o:
+            raise KvqError("param_group_blocks: the layout is not in buffer order")
+        blocks[o // 16:e // 16] = group_of[name]
+    return blocks
+
+
+def range_group(blocks, a, b):
+    """The group all blocks of the elements [a, b) share, or None when they hold more than one."""
+    piece = blocks[a // 16:(b + 15) // 16]
+    j = int(piece[0])
+    return j if bool((piece == j).all()) else None
+
+
+def lr_schedule_factor(t, warmup_steps, decay, total_steps, min_ratio):
+    """warm * dec of kvq_step_state_advance_sched for the 1-based step t, as a Python float (the host mirror: TrainEngine._lr_now)."""
+    W, r = int(warmup_steps), float(min_ratio)
+    warm = t / W if W > 0 and t < W else 1.0
+    if decay in (None, "none"):
+        return warm
+    x = min(max((t - W) / (int(total_steps) - W), 0.0), 1.0)
+    return warm * (1.0 - (1.0 - r) * x if decay == "linear" else r + (1.0 - r) * 0.5 * (1.0 + math.cos(math.pi * x)))
+
+
 class _EngineForward(torch.autograd.Function):
     """model.forward with autograd ON, on the engine's kernels: forward = TrainEngine.forward_backward(defer_backward=True),
     backward = TrainEngine.backward_from(d logits, d loss_vq).  The model's parameters are the function's inputs, so autograd
@@ -325,6 +385,8 @@ class _StepGraphs:
                         self.out["codes_revived"] = eng._rv_counter[0]
                     if eng.weight_ema is not None and final:
                         self.out["weight_ema_decay"] = eng._wema_out
+                    if eng.lr_schedule is not None and final:      # the rate of the step just applied, a view of the step state
+                        self.out["lr"] = eng._lr_out
                     ok = True
                 finally:
                     eng._cap = None
@@ -405,8 +467,19 @@ class TrainEngine:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
                  milestones=None, gamma=0.1, loss_recon_scale=1.0, loss_vq_scale=1.0, seed=1234,
                  bucket_mib=64, process_group=None, fp8_forward=None, fp8_backward=None, max_grad_norm=None, grad_accum=None,
-                 weight_ema=None, loss_ignore_pad=None):
+                 weight_ema=None, loss_ignore_pad=None, param_groups=None, decoupled_weight_decay=None, lr_warmup_steps=None,
+                 lr_decay=None, lr_total_steps=None, lr_min_ratio=None):
         self.model = model
+        # options, off by default: parameter groups, AdamW's decoupled decay, warm-up / decay of the rate
+        self._pg_spec = self.check_param_groups(param_groups, env=True)
+        self.decoupled_wd = self.check_decoupled_weight_decay(decoupled_weight_decay, env=True)
+        self.lr_schedule = self.check_lr_schedule(self.check_lr_warmup_steps(lr_warmup_steps, env=True),
+                                                  self.check_lr_decay(lr_decay, env=True),
+                                                  self.check_lr_total_steps(lr_total_steps, env=True),
+                                                  self.check_lr_min_ratio(lr_min_ratio, env=True))
+        if (self._pg_spec is not None or self.decoupled_wd) and (isinstance(weight_decay, bool) or not isinstance(weight_decay, (int, float))
+                                                                 or not 0 <= weight_decay < math.inf):      # (it fills the group table)
+            raise KvqError(f"TrainEngine: param_groups / decoupled_weight_decay need a finite weight_decay >= 0, got {weight_decay!r}")
         self.loss_ignore_pad = self.check_loss_ignore_pad(loss_ignore_pad, env=True)
         self.grad_accum = self.check_grad_accum(grad_accum, env=True)
         self.max_grad_norm = self.check_max_grad_norm(max_grad_norm, env=True)     # (before anything is laid out: a bad value changes nothing)
@@ -554,6 +627,14 @@ class TrainEngine:
         add("head.bias", head.decoder.bias, self.Vp)
         if head.decoder.weight is not dec.bert.embeddings.word_embeddings.weight:
             raise KvqError("TrainEngine expects the LM head tied to the decoder word embeddings (HF default)")
+        # names of the parameters outside the flat buffers (codebook, Gumbel projection / embedding), then the parameter groups: resolved
+        # BEFORE anything is laid out -- an unknown pattern changes nothing
+        self._aux_names = {"VectorQuantizer": ["vq.codebook"], "MultiVectorQuantizer": ["vq.codebook"],
+                           "GumbelQuantizer": ["vq.proj.weight", "vq.proj.bias", "vq.embed.weight"]}.get(self.vq_kind, [])
+        self._pg = None
+        if self._pg_spec is not None or self.decoupled_wd:
+            table, group_of = resolve_param_groups(self._pg_spec or [], [e[0] for e in entries] + self._aux_names, weight_decay)
+            self._pg = dict(table=table, group_of=group_of)
         # parameters the step never touches (pooler) stay outside the flat buffers and receive no gradient
         self.flat = FlatParams(entries, dev, self.dtype, amsgrad)
         pads = {enc.embeddings.word_embeddings.padding_idx, dec.bert.embeddings.word_embeddings.padding_idx}
@@ -574,8 +655,8 @@ class TrainEngine:
         self.aux = []
         self._bufs = {}
 
-        def add_aux(p):
-            a = dict(p=p, g=torch.zeros_like(p.data), m=torch.zeros_like(p.data), v=torch.zeros_like(p.data),
+        def add_aux(p, name):
+            a = dict(name=name, p=p, g=torch.zeros_like(p.data), m=torch.zeros_like(p.data), v=torch.zeros_like(p.data),
                      vmax=torch.zeros_like(p.data) if amsgrad else None)
             self.aux.append(a)
             return a["g"]
@@ -590,7 +671,7 @@ class TrainEngine:
                 raise KvqError(f"TrainEngine: codebook {tuple(self.E.shape)} does not match {self.G} x {self.K} x {self.Dg}")
             self.beta_vq = float(vq.beta)
             self.vq_ema = getattr(vq, "ema_decay", None) is not None     # extension: EMA codebook update instead of the gradient
-            self.gE = add_aux(self.E) if self.E.requires_grad else torch.zeros_like(self.E.data)
+            self.gE = add_aux(self.E, "vq.codebook") if self.E.requires_grad else torch.zeros_like(self.E.data)
             # the codebook in MFMA-fragment order (kvq_vq_pack_codebook): rebuilt after every codebook update -- Adam at the end
             # of the step, the EMA step, or a write from outside (noticed through the tensor version) -- not per forward call
             self._epack = torch.empty(lib().kvq_vq_packed_bytes(self.K, self.Dg, self.G), dtype=torch.uint8, device=dev) \
@@ -603,7 +684,8 @@ class TrainEngine:
             gq = model.vector_quantizer
             if gq.n_embed > 1024:
                 raise KvqError("TrainEngine: the Gumbel row kernel holds at most 1024 codes")
-            self.g_pw, self.g_pb, self.g_emb = add_aux(gq.proj.weight), add_aux(gq.proj.bias), add_aux(gq.embed.weight)
+            self.g_pw, self.g_pb, self.g_emb = (add_aux(gq.proj.weight, "vq.proj.weight"), add_aux(gq.proj.bias, "vq.proj.bias"),
+                                                add_aux(gq.embed.weight, "vq.embed.weight"))
         # extension (BASELINE.json configs[4], default off): forward GEMMs on the fp8 matrix cores; per-tensor scales -- weights from
         # the tensor itself after every update, activations delayed by one training step (kvq_fp8_quantize_delayed).
         # True / KVQ_FP8=1: the products where fp8 + the activation's quantisation pass beat the own bf16 kernel -- outputs at least
@@ -626,6 +708,20 @@ class TrainEngine:
         if self.fp8 and self.weight_ema is not None:
             raise KvqError("TrainEngine: weight_ema with fp8 forward GEMMs (fp8_forward / KVQ_FP8): evaluation under the average swaps "
                            "the weights, and their fp8 mirror would have to be re-quantised in the middle of a scale period")
+        if self.fp8 and self._pg is not None:
+            raise KvqError("TrainEngine: param_groups / decoupled_weight_decay with fp8 forward GEMMs (fp8_forward / KVQ_FP8): the Adam "
+                           "entries that write the fp8 weight mirror (kvq_adam_step_*_fp8) have no grouped form; the learning-rate "
+                           "schedule options alone compose with fp8")
+        if self._pg is not None:
+            # the tables kvq_adam_step_grouped reads, on the device, once: one byte per 16-element block of the flat buffer, and the
+            # groups' scales and decays.  Derived from the constructor's arguments: not training state.
+            fl = self.flat
+            blocks = param_group_blocks([(n, o) for n, (o, _, _) in fl.seg.items()], fl.n, self._pg["group_of"])
+            self._pg.update(blocks_host=blocks, blocks=blocks.to(dev),
+                            scale=torch.tensor([g["lr_scale"] for g in self._pg["table"]], dtype=torch.float32, device=dev),
+                            wd=torch.tensor([g["weight_decay"] for g in self._pg["table"]], dtype=torch.float32, device=dev),
+                            range_group={})
+        self._lr_out = self._state[1:2].view(torch.float32)[0]      # the step state's lr, a view: train_step hands out copies
         self._fp8_fused = fp8_forward == "fused"
         self._fp8_all = fp8_forward in ("all", "fused")
         self._x8 = {}                      # data_ptr of a bf16 activation -> its fp8 copy, left by the producer for ONE fp8 GEMM
@@ -765,6 +861,8 @@ class TrainEngine:
         """MultiStepLR ticked once per optimiser step (Trainer.py:114-115): the s-th step (1-based) sees s-1 ticks."""
         ticks = self.step_count - 1
         k = sum(1 for m in self.milestones if ticks >= m)
+        if self.lr_schedule is not None:          # warm-up / decay of kvq_step_state_advance_sched, mirrored on the host
+            return self.lr * (self.gamma ** k) * lr_schedule_factor(self.step_count, *self.lr_schedule)
         return self.lr * (self.gamma ** k)
 
     def _site(self):
@@ -2319,6 +2417,147 @@ class TrainEngine:
             raise KvqError(f"TrainEngine: weight_ema must be None or a float in (0, 1), got {v!r}")
         return float(v)
 
+    # ---- parameter groups, decoupled weight decay, learning-rate schedule -----------------------------------
+    @staticmethod
+    def _env_value(name, parse, what):
+        s = os.environ.get(name, "")
+        if s == "":
+            return None
+        try:
+            return parse(s)
+        except ValueError:
+            raise KvqError(f"TrainEngine: {name} must be {what}, got {s!r}") from None
+
+    @staticmethod
+    def check_param_groups(v, env=False):
+        """None (off), or the normalised list of {"match": [patterns], "lr_scale": float, "weight_decay": float | None (the engine's)}
+        a TrainEngine(param_groups=...) accepts; anything else raises KvqError naming the offender.  env: None means KVQ_PARAM_GROUPS
+        (JSON) from the environment (unset or empty: off).  Whether a pattern matches a parameter is checked by the constructor, which
+        knows the names.  lr_scale 0 is allowed and does NOT freeze a group: its moments still move."""
+        if v is None and env:
+            import json
+            v = TrainEngine._env_value("KVQ_PARAM_GROUPS", json.loads, "a JSON list of groups")
+        if v is None:
+            return None
+        if not isinstance(v, (list, tuple)):
+            raise KvqError(f"TrainEngine: param_groups must be None or a list of dicts, got {v!r}")
+        if len(v) > MAX_PARAM_GROUPS:
+            raise KvqError(f"TrainEngine: param_groups holds {len(v)} groups; at most {MAX_PARAM_GROUPS} beside the default group")
+        out = []
+        for j, g in enumerate(v):
+            if not isinstance(g, dict) or "match" not in g or set(g) - {"match", "lr_scale", "weight_decay"}:
+                raise KvqError(f"TrainEngine: param_groups[{j}] must be a dict with \"match\" and optionally \"lr_scale\", "
+                               f"\"weight_decay\", got {g!r}")
+            pats = [g["match"]] if isinstance(g["match"], str) else g["match"]
+            if not isinstance(pats, (list, tuple)) or not pats or not all(isinstance(p, str) and p for p in pats):
+                raise KvqError(f"TrainEngine: param_groups[{j}][\"match\"] must be a pattern or a non-empty list of patterns, got {g['match']!r}")
+            vals = {}
+            for key, default in (("lr_scale", 1.0), ("weight_decay", None)):
+                x = g.get(key, default)
+                if x is not None and (isinstance(x, bool) or not isinstance(x, (int, float)) or not 0 <= x < math.inf):
+                    raise KvqError(f"TrainEngine: param_groups[{j}][{key!r}] must be a finite float >= 0, got {x!r}")
+                vals[key] = None if x is None else float(x)
+            out.append(dict(match=list(pats), **vals))
+        return out
+
+    @staticmethod
+    def check_decoupled_weight_decay(v, env=False):
+        """The bool a TrainEngine(decoupled_weight_decay=...) accepts (False: off, the coupled L2 term); env: None means KVQ_DECOUPLED_WD
+        (0 / 1) from the environment."""
+        if v is None and env and os.environ.get("KVQ_DECOUPLED_WD", "") != "":
+            s = os.environ["KVQ_DECOUPLED_WD"]
+            if s not in ("0", "1"):
+                raise KvqError(f"TrainEngine: KVQ_DECOUPLED_WD (decoupled_weight_decay) must be 0 or 1, got {s!r}")
+            v = s == "1"
+        if v is None:
+            return False
+        if not isinstance(v, bool):
+            raise KvqError(f"TrainEngine: decoupled_weight_decay must be None, False or True, got {v!r}")
+        return v
+
+    @staticmethod
+    def check_lr_warmup_steps(v, env=False):
+        """The int >= 0 a TrainEngine(lr_warmup_steps=...) accepts (0: off); env: None means KVQ_LR_WARMUP_STEPS."""
+        if v is None and env:
+            v = TrainEngine._env_value("KVQ_LR_WARMUP_STEPS", int, "an integer >= 0")
+        if v is None:
+            return 0
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise KvqError(f"TrainEngine: lr_warmup_steps must be None or an integer >= 0, got {v!r}")
+        return v
+
+    @staticmethod
+    def check_lr_decay(v, env=False):
+        """None (off), "linear" or "cosine"; "none" means off; env: None means KVQ_LR_DECAY."""
+        if v is None and env:
+            v = TrainEngine._env_value("KVQ_LR_DECAY", str, "none, linear or cosine")
+        if v is None or v == "none":
+            return None
+        if v not in ("linear", "cosine"):
+            raise KvqError(f"TrainEngine: lr_decay must be None, \"none\", \"linear\" or \"cosine\", got {v!r}")
+        return v
+
+    @staticmethod
+    def check_lr_total_steps(v, env=False):
+        """None, or the int >= 1 a TrainEngine(lr_total_steps=...) accepts; env: None means KVQ_LR_TOTAL_STEPS."""
+        if v is None and env:
+            v = TrainEngine._env_value("KVQ_LR_TOTAL_STEPS", int, "an integer >= 1")
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise KvqError(f"TrainEngine: lr_total_steps must be None or an integer >= 1, got {v!r}")
+        return v
+
+    @staticmethod
+    def check_lr_min_ratio(v, env=False):
+        """None, or the float in [0, 1] a TrainEngine(lr_min_ratio=...) accepts; env: None means KVQ_LR_MIN_RATIO."""
+        if v is None and env:
+            v = TrainEngine._env_value("KVQ_LR_MIN_RATIO", float, "a float in [0, 1]")
+        if v is None:
+            return None
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1:
+            raise KvqError(f"TrainEngine: lr_min_ratio must be None or a float in [0, 1], got {v!r}")
+        return float(v)
+
+    @staticmethod
+    def check_lr_schedule(warmup_steps, decay, total_steps, min_ratio):
+        """The four checked schedule options together: None when no warm-up and no decay is asked for, else the tuple
+        (warmup_steps, "none" | "linear" | "cosine", total_steps, min_ratio) of kvq_step_state_advance_sched.  A decay needs
+        lr_total_steps > lr_warmup_steps; lr_total_steps / lr_min_ratio without a decay mean nothing and are refused."""
+        if decay is None:
+            if total_steps is not None or min_ratio is not None:
+                raise KvqError("TrainEngine: lr_total_steps / lr_min_ratio without lr_decay (\"linear\" or \"cosine\")")
+            return (warmup_steps, "none", 0, 0.0) if warmup_steps > 0 else None
+        if total_steps is None or total_steps <= warmup_steps:
+            raise KvqError(f"TrainEngine: lr_decay={decay!r} needs lr_total_steps > lr_warmup_steps, got {total_steps!r} and {warmup_steps!r}")
+        return (warmup_steps, decay, total_steps, 0.0 if min_ratio is None else min_ratio)
+
+    def param_names(self):
+        """Every name a param_groups pattern is matched against: the flat buffer's entries in buffer order, then the parameters
+        outside it (vq.codebook; vq.proj.weight, vq.proj.bias, vq.embed.weight of a Gumbel quantiser)."""
+        return list(self.flat.seg) + list(self._aux_names)
+
+    def param_group_of(self, name):
+        """The group (0 = the default group) the parameter `name` is updated under."""
+        if name not in self.flat.seg and name not in self._aux_names:
+            raise KvqError(f"TrainEngine.param_group_of: no parameter named {name!r} (param_names() lists them)")
+        return self._pg["group_of"][name] if self._pg is not None else 0
+
+    def param_group_table(self):
+        """One dict per group, group 0 first: group, match, lr_scale, weight_decay (resolved), names (members), elements (their
+        parameter elements, frozen ones included).  Without param_groups: the one default group."""
+        numel = {n: int(c) for n, (_, c, _) in self.flat.seg.items()}
+        if self.has_vq and self.vq_kind != "GumbelQuantizer":
+            numel["vq.codebook"] = self.E.numel()
+        elif self.has_vq:
+            gq = self.model.vector_quantizer
+            numel.update({"vq.proj.weight": gq.proj.weight.numel(), "vq.proj.bias": gq.proj.bias.numel(),
+                          "vq.embed.weight": gq.embed.weight.numel()})
+        table = self._pg["table"] if self._pg is not None else \
+            [dict(group=0, match=[], lr_scale=1.0, weight_decay=float(self.wd), names=self.param_names())]
+        return [dict(group=g["group"], match=list(g["match"]), lr_scale=g["lr_scale"], weight_decay=g["weight_decay"],
+                     names=len(g["names"]), elements=sum(numel[n] for n in g["names"])) for g in table]
+
     @property
     def weight_ema_updates(self):
         """Updates the average has taken so far (weight_ema only, 0 otherwise; synchronises).  A skipped step applies none."""
@@ -2467,6 +2706,20 @@ class TrainEngine:
                     check(lib().kvq_adam_step_guarded_fp8(*args, self._guard.data_ptr(), stream_ptr()), "kvq_adam_step_guarded_fp8")
                 else:
                     check(lib().kvq_adam_step_dev_fp8(*args, stream_ptr()), "kvq_adam_step_dev_fp8")
+            elif a < b and self._pg is not None:
+                # parameter groups: still ONE launch per range.  A range whose blocks share a group passes no block table (the work of
+                # adam_step_dev); any other looks its groups up per 16-element block of the flat buffer, indexed from element a.
+                pg = self._pg
+                if (a, b) not in pg["range_group"]:
+                    pg["range_group"][(a, b)] = range_group(pg["blocks_host"], a, b)
+                j = pg["range_group"][(a, b)]
+                nnops.adam_step_grouped(fl.master[a:b], grad[a:b], fl.m[a:b], fl.v[a:b], self._state, b1, b2, self.eps, self.wd,
+                                        vmax=fl.vmax[a:b] if fl.vmax is not None else None,
+                                        shadow=fl.shadow[a:b] if fl.shadow is not fl.master else None, guard=self._guard,
+                                        block_group=pg["blocks"] if j is None else None, first_element=a,
+                                        group_lr_scale=pg["scale"] if j is None else pg["scale"][j:j + 1],
+                                        group_wd=pg["wd"] if j is None else pg["wd"][j:j + 1],
+                                        n_groups=len(pg["table"]) if j is None else 1, decoupled=self.decoupled_wd)
             elif a < b:
                 nnops.adam_step_dev(fl.master[a:b], grad[a:b], fl.m[a:b], fl.v[a:b], self._state, b1, b2, self.eps, self.wd,
                                     vmax=fl.vmax[a:b] if fl.vmax is not None else None,
@@ -2495,7 +2748,7 @@ class TrainEngine:
                 self._eager(self._exchange_tail)
                 self._gn_pieces(0, cut)
             self._gn_finish()
-            nnops.step_state_advance(self._state, self.lr, self.gamma, self.milestones, b1, b2)
+            self._advance_state()
             self._adam_ranges(0, fl.n)
             self._adam_aux()
             self._revive_apply()
@@ -2503,7 +2756,7 @@ class TrainEngine:
             self._after_update()
             return
         # step += 1, lr after the milestones, bias corrections: computed on the device, read there by the Adam kernels
-        nnops.step_state_advance(self._state, self.lr, self.gamma, self.milestones, b1, b2)
+        self._advance_state()
         self._adam_ranges(cut, fl.n)                  # multi-GPU: runs while the head of the buffer is still being reduced
         if self._dp:
             self._eager(self._exchange_tail)
@@ -2513,10 +2766,26 @@ class TrainEngine:
         self._weight_ema_update()
         self._after_update()
 
+    def _advance_state(self):
+        """step += 1, lr and bias corrections of the step on the device; the _sched entry only when a schedule option is on."""
+        b1, b2 = self.betas
+        if self.lr_schedule is None:
+            nnops.step_state_advance(self._state, self.lr, self.gamma, self.milestones, b1, b2)
+            return
+        W, kind, T, r = self.lr_schedule
+        nnops.step_state_advance_sched(self._state, self.lr, self.gamma, self.milestones, b1, b2, warmup_steps=W,
+                                       decay_kind=nnops.LR_DECAY_KINDS[kind], total_steps=T, min_ratio=r)
+
     def _adam_aux(self):
         b1, b2 = self.betas
         for a in self.aux:
-            if a["p"].requires_grad:
+            if a["p"].requires_grad and self._pg is not None:         # the one-group form with the aux parameter's group
+                j = self._pg["group_of"][a["name"]]
+                nnops.adam_step_grouped(a["p"].data.view(-1), a[self._aux_src].view(-1), a["m"].view(-1), a["v"].view(-1), self._state,
+                                        b1, b2, self.eps, self.wd, vmax=a["vmax"].view(-1) if a["vmax"] is not None else None,
+                                        guard=self._guard, group_lr_scale=self._pg["scale"][j:j + 1], group_wd=self._pg["wd"][j:j + 1],
+                                        n_groups=1, decoupled=self.decoupled_wd)
+            elif a["p"].requires_grad:
                 nnops.adam_step_dev(a["p"].data.view(-1), a[self._aux_src].view(-1), a["m"].view(-1), a["v"].view(-1), self._state,
                                     b1, b2, self.eps, self.wd, vmax=a["vmax"].view(-1) if a["vmax"] is not None else None,
                                     guard=self._guard)
@@ -2577,6 +2846,10 @@ class TrainEngine:
             "world": int(self.world),
             **({"weight_ema": float(self.weight_ema)} if self.weight_ema is not None else {}),     # off: exactly the keys of before
             **({"loss_ignore_pad": True} if self.loss_ignore_pad else {}),
+            **({"param_groups": [[list(g["match"]), g["lr_scale"], g["weight_decay"], list(g["names"])] for g in self._pg["table"]]}
+               if self._pg_spec is not None else {}),
+            **({"decoupled_weight_decay": True} if self.decoupled_wd else {}),
+            **({"lr_schedule": list(self.lr_schedule)} if self.lr_schedule is not None else {}),
         }
 
     def _state_slots(self, present) -> dict:
@@ -2885,6 +3158,8 @@ class TrainEngine:
             out["codes_revived"] = self._rv_counter[0].clone()
         if self.weight_ema is not None and final:
             out["weight_ema_decay"] = self._wema_out.clone()
+        if self.lr_schedule is not None and final:
+            out["lr"] = self._lr_out.clone()
         out["optimizer_step"] = final
         return out
 

@@ -368,6 +368,45 @@ def step_state_advance(step_state, lr0, gamma, milestones, beta1, beta2):
                                        stream_ptr()), "kvq_step_state_advance")
 
 
+LR_DECAY_KINDS = {"none": 0, "linear": 1, "cosine": 2}       # decay_kind of kvq_step_state_advance_sched
+
+
+def step_state_advance_sched(step_state, lr0, gamma, milestones, beta1, beta2, warmup_steps=0, decay_kind=0, total_steps=0, min_ratio=0.0):
+    """step_state_advance with a linear warm-up over `warmup_steps` steps and a linear (1) / cosine (2) decay to min_ratio * lr0 at
+    `total_steps` (include/kvq.h); warmup_steps 0 and decay_kind 0 give step_state_advance's bits."""
+    import ctypes
+    ms = [int(x) for x in milestones]
+    arr = (ctypes.c_int64 * max(len(ms), 1))(*ms)
+    check(lib().kvq_step_state_advance_sched(step_state.data_ptr(), float(lr0), float(gamma), arr, len(ms), float(beta1), float(beta2),
+                                             int(warmup_steps), int(decay_kind), int(total_steps), float(min_ratio), stream_ptr()),
+          "kvq_step_state_advance_sched")
+
+
+def adam_step_grouped(p32, g, m, v, step_state, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, vmax=None, shadow=None, grad_scale=1.0,
+                      guard=None, block_group=None, first_element=0, group_lr_scale=None, group_wd=None, n_groups=1, decoupled=False):
+    """adam_step_dev with parameter groups (include/kvq.h): block_group (uint8, one entry per 16-element block of the flat buffer the
+    range was cut from; p32[0] is element first_element of that buffer) names each block's entry of the f32 device tables
+    group_lr_scale / group_wd (None: scale 1 / weight_decay for every group).  block_group None: entry 0 for the whole launch.
+    decoupled: torch.optim.AdamW's decay instead of the coupled L2 term."""
+    n = p32.numel()
+    for t, dt in ((block_group, torch.uint8), (group_lr_scale, torch.float32), (group_wd, torch.float32)):
+        if t is not None and (t.dtype != dt or not t.is_cuda or not t.is_contiguous()):
+            raise KvqError(f"adam_step_grouped: the group tables are contiguous device tensors (uint8 blocks, f32 scales and decays)")
+    if block_group is not None and (first_element % 16 or (first_element + n + 15) // 16 > block_group.numel()):
+        raise KvqError(f"adam_step_grouped: elements [{first_element}, {first_element + n}) need a first element that is a multiple of 16 "
+                       f"and {(first_element + n + 15) // 16} table blocks, the table has {block_group.numel()}")
+    for t in (group_lr_scale, group_wd):
+        if t is not None and t.numel() < n_groups:
+            raise KvqError(f"adam_step_grouped: {n_groups} groups, a table of {t.numel()}")
+    args = (p32.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(vmax), _p(shadow), n, io_dtype_of(g), step_state.data_ptr(),
+            float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale), _p(block_group), int(first_element),
+            _p(group_lr_scale), _p(group_wd), int(n_groups), int(bool(decoupled)))
+    if guard is not None:
+        check(lib().kvq_adam_step_grouped_guarded(*args, _guard_ptr(guard), stream_ptr()), "kvq_adam_step_grouped_guarded")
+        return
+    check(lib().kvq_adam_step_grouped(*args, stream_ptr()), "kvq_adam_step_grouped")
+
+
 def read_step_state(step_state):
     """(step, lr, bc1, bc2s) -- synchronises; for tests and logging."""
     raw = step_state.cpu()

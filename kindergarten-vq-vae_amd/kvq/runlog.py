@@ -125,3 +125,21 @@ def weight_ema_epoch_record(engine, last_decay=None, stage: str = "train"):
         return None
     return {f"{stage}/weight_ema_decay": float(last_decay) if last_decay is not None else None,
             f"{stage}/weight_ema_updates": int(engine.weight_ema_updates)}
+
+
+def param_groups_line(engine):
+    """One line for the run's log with the engine's parameter-group table (pattern, lr scale, weight decay, parameter elements per
+    group) | None without an engine or with param_groups / decoupled_weight_decay off."""
+    if engine is None or getattr(engine, "_pg", None) is None:
+        return None
+    cells = [f"{g['group']}: {', '.join(g['match']) if g['match'] else '(everything else)'} lr x{g['lr_scale']:g} wd {g['weight_decay']:g} "
+             f"{g['elements']} elements" for g in engine.param_group_table()]
+    return f"parameter groups ({'decoupled' if engine.decoupled_wd else 'coupled'} weight decay) | " + " | ".join(cells)
+
+
+def lr_epoch_record(engine, last_lr=None, stage: str = "train"):
+    """End of a training stage, after its statistics were read: {"<stage>/lr": the learning rate of the stage's last optimiser step,
+    from the device scalar the step handed out} | None without a learning-rate schedule (lr_warmup_steps / lr_decay)."""
+    if engine is None or getattr(engine, "lr_schedule", None) is None or last_lr is None:
+        return None
+    return {f"{stage}/lr": float(last_lr)}

@@ -30,7 +30,7 @@ from torch import Tensor, no_grad, save
 from common.consts import *  # noqa: F401,F403
 from common.tensor_utils import replace_pct_rand_values
 from kvq.runlog import (drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note, optimizer_steps_epoch,
-                        weight_ema_epoch_record, weight_ema_scope)
+                        weight_ema_epoch_record, weight_ema_scope, lr_epoch_record, param_groups_line)
 from kvq.train_state import check_every, restore_trainer, save_train_state, trainer_state
 
 
@@ -104,6 +104,8 @@ def step(device, model, tokenizer_encoder, tokenizer_decoder,
         stats["optimizer_step"] = out["optimizer_step"]
     if engine is not None and "weight_ema_decay" in out:  # weight_ema: the decay this step's update used, a device scalar like the others
         stats["weight_ema_decay_step"] = out["weight_ema_decay"]
+    if engine is not None and "lr" in out:            # lr_warmup_steps / lr_decay: the rate this step was applied under, a device scalar
+        stats["lr_step"] = out["lr"]
     return stats, input_ids_encoder, input_ids_decoder, recon_ids, labels
 
 
@@ -118,6 +120,8 @@ def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batc
     optimizer_step_note(stats_stage_run, stats_step)
     if "weight_ema_decay_step" in stats_step:     # the last one of the stage is what the epoch's line reports
         stats_stage_run["weight_ema_decay_last"] = stats_step["weight_ema_decay_step"]
+    if "lr_step" in stats_step:                   # likewise the learning rate under a schedule: read once, at the end of the epoch
+        stats_stage_run["lr_last"] = stats_step["lr_step"]
     return stats_stage_run
 
 
@@ -284,6 +288,8 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
     first_epoch = 1
     if resume is not None:
         first_epoch, stats_train_best, stats_val_best, hist, skipped = restore_trainer(resume, decoded_sentences, dl_train)
+    if console is not None and param_groups_line(engine) is not None:      # param_groups: the resolved table, once per run
+        console.print("    | " + param_groups_line(engine))
     for epoch in range(first_epoch, n_epochs + 1):
         if prg is not None:
             prg.reset(tasks[0]); prg.reset(tasks[1])
@@ -305,6 +311,11 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
             if console is not None:
                 console.print(f"    | weight EMA decay: {wema_rec['train/weight_ema_decay']} | updates: {wema_rec['train/weight_ema_updates']}"
                               f"{'' if weight_ema_eval else ' | evaluation on the live weights'}")
+        lr_rec = lr_epoch_record(engine, run.pop("lr_last", None))                        # lr schedule: the epoch's last rate
+        if lr_rec is not None:
+            wandb_run.log({"epoch": epoch, **lr_rec})
+            if console is not None:
+                console.print(f"    | lr: {lr_rec['train/lr']:.6e}")
         # sentences/s of THIS rank's train stage, loop and all (end_of_epoch_stats_update has just turned the device sums into
         # floats: the stage's kernels have finished).  An extra log entry, not one of the reference's keys.
         wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": s, "perf/optimizer_steps": n_opt,

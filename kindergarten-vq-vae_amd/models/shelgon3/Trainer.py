@@ -25,7 +25,7 @@ from torch import Tensor, no_grad, save
 
 from common.consts import *  # noqa: F401,F403  (colours / emoji)
 from kvq.runlog import (codes_revived_note, drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note,
-                        optimizer_steps_epoch, revive_epoch_record, weight_ema_epoch_record, weight_ema_scope)
+                        optimizer_steps_epoch, revive_epoch_record, weight_ema_epoch_record, weight_ema_scope, lr_epoch_record, param_groups_line)
 from kvq.train_state import check_every, restore_trainer, save_train_state, trainer_state
 
 
@@ -65,6 +65,8 @@ def step(device, model, tokenizer, tokenizer_add_special_tokens: bool, opt,
             stats["optimizer_step"] = out["optimizer_step"]
         if "weight_ema_decay" in out:             # weight_ema: the decay this step's update used, a device scalar like the others
             stats["weight_ema_decay_step"] = out["weight_ema_decay"]
+        if "lr" in out:                           # lr_warmup_steps / lr_decay: the rate this step was applied under, a device scalar
+            stats["lr_step"] = out["lr"]
         return stats, input_ids, out["recon_ids"]
 
     loss_vq_step, metric_perp_step, _indices, loss_recon_step, acc_step, recon_ids = \
@@ -110,6 +112,8 @@ def end_of_step_stats_update(stats_stage_run: dict, stats_step: dict, n_els_batc
     optimizer_step_note(stats_stage_run, stats_step)
     if "weight_ema_decay_step" in stats_step:     # the last one of the stage is what the epoch's line reports
         stats_stage_run["weight_ema_decay_last"] = stats_step["weight_ema_decay_step"]
+    if "lr_step" in stats_step:                   # likewise the learning rate under a schedule: read once, at the end of the epoch
+        stats_stage_run["lr_last"] = stats_step["lr_step"]
     return stats_stage_run
 
 
@@ -265,6 +269,8 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
     first_epoch = 1
     if resume is not None:
         first_epoch, stats_train_best, stats_val_best, history, skipped = restore_trainer(resume, decoded_sentences, dl_train)
+    if console is not None and param_groups_line(engine) is not None:      # param_groups: the resolved table, once per run
+        console.print("    | " + param_groups_line(engine))
     for epoch in range(first_epoch, n_epochs + 1):
         if tasks:
             prg.reset(tasks[1]); prg.reset(tasks[2])
@@ -294,6 +300,11 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
             if console is not None:
                 console.print(f"    | weight EMA decay: {wema_rec['train/weight_ema_decay']} | updates: {wema_rec['train/weight_ema_updates']}"
                               f"{'' if weight_ema_eval else ' | evaluation on the live weights'}")
+        lr_rec = lr_epoch_record(engine, run.pop("lr_last", None))                        # lr schedule: the epoch's last rate
+        if lr_rec is not None:
+            wandb_run.log({"epoch": epoch, **lr_rec})
+            if console is not None:
+                console.print(f"    | lr: {lr_rec['train/lr']:.6e}")
         # sentences/s of THIS rank's train stage, loop and all (end_of_epoch_stats_update has just turned the device sums into
         # floats: the stage's kernels have finished).  An extra log entry, not one of the reference's keys.
         wandb_run.log({"epoch": epoch, "perf/train_s": _time.perf_counter() - t_stage, "perf/train_steps": n_steps, "perf/optimizer_steps": n_opt,

@@ -40,6 +40,12 @@ GRAD_ACCUM_STEPS = 1                 # int >= 1: train_step calls (micro-batches
 WEIGHT_EMA_DECAY = None            # None (off) | float in (0, 1): the engine keeps an f32 moving average of the trained weights, updated behind Adam inside the step (the decay warms up as min(decay, (1 + t) / (10 + t))); KVQ_WEIGHT_EMA; DESIGN.md section 5f
 WEIGHT_EMA_EVAL = True              # with WEIGHT_EMA_DECAY: validation, the best-val checkpoints and the test stage run under the average (False: the average is kept and saved with the training state, evaluation reads the live weights)
 LOSS_IGNORE_PAD = False             # False | True: the engine step takes the reconstruction loss, the accuracy and the per-sentence accuracy over the tokens whose target is not the pad id (F.cross_entropy's ignore_index) instead of over all B*S positions; KVQ_LOSS_IGNORE_PAD; DESIGN.md section 5g
+PARAM_GROUPS = None                 # None (off) | list of {"match": pattern | [patterns], "lr_scale": float >= 0 (1), "weight_decay": float >= 0 (WEIGHT_DECAY)}: fnmatch patterns over the engine's parameter names (engine.param_names()), first match wins, the rest trains under LR and WEIGHT_DECAY; e.g. [{"match": ["*.b", "*.ln.w", "*.ln2.w", "head.bias"], "weight_decay": 0.0}] (= kvq.engine.NO_DECAY); KVQ_PARAM_GROUPS (JSON); DESIGN.md section 5h
+DECOUPLED_WEIGHT_DECAY = False      # False | True: torch.optim.AdamW's decoupled decay instead of Adam's coupled L2 term, in the engine's Adam kernel; KVQ_DECOUPLED_WD (0 / 1)
+LR_WARMUP_STEPS = 0                 # int >= 0: the rate climbs as t / LR_WARMUP_STEPS over the first optimiser steps (0: off); multiplies the MultiStepLR factor
+LR_DECAY = None                     # None | "linear" | "cosine": decay from the end of the warm-up to LR_MIN_RATIO * LR at step LR_TOTAL_STEPS, where it stays
+LR_TOTAL_STEPS = None               # int > LR_WARMUP_STEPS, with LR_DECAY
+LR_MIN_RATIO = None                 # float in [0, 1], with LR_DECAY (None: 0)
 
 VQ_MODE = "VectorQuantizer"          # VectorQuantizer | GumbelQuantizer | MultiVectorQuantizer (extension: VQ_N_FACTORS codebooks)
 VQ_N_FACTORS = 1                     # MultiVectorQuantizer: codebooks = slices of the encoder output (must divide VQ_E_DIM)
@@ -130,6 +136,38 @@ if LOSS_IGNORE_PAD in (0, 1) and not isinstance(LOSS_IGNORE_PAD, bool) and _os.e
     LOSS_IGNORE_PAD = bool(LOSS_IGNORE_PAD)      # the environment spells the switch 0 / 1, as TrainEngine reads it
 if not isinstance(LOSS_IGNORE_PAD, bool):
     raise ValueError(f"LOSS_IGNORE_PAD (KVQ_LOSS_IGNORE_PAD) must be True or False (0 or 1 in the environment), got {LOSS_IGNORE_PAD!r}")
+_v = _os.environ.get("KVQ_DECOUPLED_WD", "").strip()      # the variable TrainEngine itself reads; it wins over KVQ_DECOUPLED_WEIGHT_DECAY; empty = unset
+if _v:
+    DECOUPLED_WEIGHT_DECAY = {"0": False, "1": True}.get(_v, _v)
+if isinstance(DECOUPLED_WEIGHT_DECAY, str) and not DECOUPLED_WEIGHT_DECAY.strip():
+    DECOUPLED_WEIGHT_DECAY = False
+if isinstance(PARAM_GROUPS, str):        # KVQ_PARAM_GROUPS is JSON, as TrainEngine reads it (a list of plain dicts is a python literal as well); empty = off
+    import json as _json
+    try:
+        PARAM_GROUPS = _json.loads(PARAM_GROUPS) if PARAM_GROUPS.strip() else None
+    except ValueError:
+        raise ValueError(f"PARAM_GROUPS (KVQ_PARAM_GROUPS) must be a JSON list of groups, got {PARAM_GROUPS!r}") from None
+for _k in ("LR_WARMUP_STEPS", "LR_DECAY", "LR_TOTAL_STEPS", "LR_MIN_RATIO"):      # KVQ_<NAME>= (empty) = unset, as TrainEngine reads the variables
+    if isinstance(globals()[_k], str) and not globals()[_k].strip():
+        globals()[_k] = 0 if _k == "LR_WARMUP_STEPS" else None
+if (PARAM_GROUPS, DECOUPLED_WEIGHT_DECAY, LR_WARMUP_STEPS, LR_DECAY, LR_TOTAL_STEPS, LR_MIN_RATIO) != (None, False, 0, None, None, None):
+    # one set of rules: the engine's own check_* methods (static, no device needed) judge the values; a refusal names the constant
+    def _check_optimiser_options():
+        from kvq._ffi import KvqError
+        from kvq.engine import TrainEngine as E
+        checked, what = {}, None
+        try:
+            for what, check in (("PARAM_GROUPS", E.check_param_groups), ("DECOUPLED_WEIGHT_DECAY", E.check_decoupled_weight_decay),
+                                ("LR_WARMUP_STEPS", E.check_lr_warmup_steps), ("LR_DECAY", E.check_lr_decay),
+                                ("LR_TOTAL_STEPS", E.check_lr_total_steps), ("LR_MIN_RATIO", E.check_lr_min_ratio)):
+                checked[what] = check(globals()[what])
+            what = "LR_TOTAL_STEPS / LR_MIN_RATIO"
+            E.check_lr_schedule(checked["LR_WARMUP_STEPS"], checked["LR_DECAY"], checked["LR_TOTAL_STEPS"], checked["LR_MIN_RATIO"])
+        except KvqError as e:
+            raise ValueError(f"{what} (KVQ_{what.split(' ')[0]}): {e}") from None
+        return checked["LR_DECAY"]
+    LR_DECAY = _check_optimiser_options()        # ("none" means None)
+    del _check_optimiser_options
 if isinstance(TRAIN_STATE_EVERY_EPOCHS, bool) or not isinstance(TRAIN_STATE_EVERY_EPOCHS, int) or TRAIN_STATE_EVERY_EPOCHS < 1:
     raise ValueError(f"TRAIN_STATE_EVERY_EPOCHS (KVQ_TRAIN_STATE_EVERY_EPOCHS) must be an integer >= 1, got {TRAIN_STATE_EVERY_EPOCHS!r}")
 if isinstance(RESUME_FROM, str) and not RESUME_FROM.strip():      # KVQ_RESUME_FROM= (empty) = unset

@@ -119,7 +119,10 @@ def main():
                              max_grad_norm=MAX_GRAD_NORM,                             # (None: off, or KVQ_MAX_GRAD_NORM)
                              grad_accum=GRAD_ACCUM_STEPS,                             # (1: off; the configuration has read KVQ_GRAD_ACCUM)
                              weight_ema=WEIGHT_EMA_DECAY,                             # (None: off; the configuration has read KVQ_WEIGHT_EMA)
-                             loss_ignore_pad=LOSS_IGNORE_PAD)                         # (the configuration has read KVQ_LOSS_IGNORE_PAD)
+                             loss_ignore_pad=LOSS_IGNORE_PAD,                         # (the configuration has read KVQ_LOSS_IGNORE_PAD)
+                             param_groups=PARAM_GROUPS, decoupled_weight_decay=DECOUPLED_WEIGHT_DECAY,      # (the
+                             lr_warmup_steps=LR_WARMUP_STEPS, lr_decay=LR_DECAY,                            # configuration has read their
+                             lr_total_steps=LR_TOTAL_STEPS, lr_min_ratio=LR_MIN_RATIO)                      # KVQ_* variables)
         if TOKEN_CACHE:
             for c in caches:          # the packed sort files the MODEL's padding row under -1 (not the tokenizer's pad id)
                 c.packed_pad_id = engine.pad_idx
@@ -131,6 +134,9 @@ def main():
         model.loss_ignore_index = model.decoder.bert.embeddings.word_embeddings.padding_idx
         if model.loss_ignore_index is None:
             raise SystemExit("LOSS_IGNORE_PAD (KVQ_LOSS_IGNORE_PAD) needs word embeddings with a padding_idx")
+    if engine is None and (PARAM_GROUPS is not None or DECOUPLED_WEIGHT_DECAY or LR_WARMUP_STEPS > 0 or LR_DECAY is not None):
+        # groups, the decoupled decay and the schedule live in the engine's Adam / step-state kernels: no silent run under `opt`'s rule
+        raise SystemExit("PARAM_GROUPS / DECOUPLED_WEIGHT_DECAY / LR_WARMUP_STEPS / LR_DECAY need the engine (USE_ENGINE and a model shape it supports)")
     if engine is None and WEIGHT_EMA_DECAY is not None:      # the average is built inside the engine's step: no silent run without it
         raise SystemExit("WEIGHT_EMA_DECAY (KVQ_WEIGHT_EMA) needs the engine (USE_ENGINE and a model shape it supports)")
 
