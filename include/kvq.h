@@ -598,7 +598,7 @@ int kvq_adam_step_guarded_fp8(float* p, const void* g, float* m, float* v, float
                               void* w8_mirror, const int* span_segment, const float* seg_scale, const int64_t* seg_off,
                               const int64_t* seg_n, int nseg, int64_t first_element, const void* guard, void* stream);
 
-/* ---- parameter groups, decoupled weight decay and a learning-rate schedule in the step (csrc/kvq_nn.hip) ------------------------
+/* ---- parameter groups, decoupled weight decay and a learning-rate schedule in the step (csrc/kvq_adam.hip) ------------------------
  * Extension, off by default (TrainEngine(param_groups=..., decoupled_weight_decay=..., lr_warmup_steps=..., lr_decay=...)).
  * kvq_adam_step_grouped[_guarded]  kvq_adam_step_dev [kvq_adam_step_guarded] with a learning-rate scale s_j and a weight decay wd_j
  *                          per parameter GROUP j, looked up inside the one launch.  block_group[(first_element + e) >> 4] names

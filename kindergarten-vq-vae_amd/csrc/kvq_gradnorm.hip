@@ -4,7 +4,7 @@
 //     kvq_grad_sumsq_partial     sum of squares of one piece of the gradient -> GN_PARTIALS f64 partial sums
 //     kvq_grad_guard_finalize    all partials -> the guard state: norm, the clipping coefficient of
 //                                torch.nn.utils.clip_grad_norm_, and the skip flag of a step whose gradient is not finite
-// and kvq_adam_step_guarded* (csrc/kvq_nn.hip) multiply the gradient by guard->coef or, with guard->skip set, store nothing.
+// and kvq_adam_step_guarded* (csrc/kvq_adam.hip) multiply the gradient by guard->coef or, with guard->skip set, store nothing.
 // Everything is a kernel launch on the step's stream reading and writing device memory: no host round trip, nothing a captured
 // step would have to patch.
 //

@@ -926,6 +926,7 @@ class TrainEngine:
         self._w8_span = torch.from_numpy(fp8_span_table(offs, ns, fl.n)).to(self.dev)
         self._w8_amax = torch.zeros(len(keys), dtype=torch.float32, device=self.dev)
         self._w8_scale = torch.ones(len(keys), dtype=torch.float32, device=self.dev)
+        self._w8_adam = (self._w8, self._w8_span, self._w8_scale, self._w8_off, self._w8_n, len(keys))   # nnops.adam_step_dev(fp8=)
         if self.fp8_backward:
             self._fp8_bwd_setup(keys, offs, ns)
         self._fp8_quantize_weights()
@@ -2687,43 +2688,41 @@ class TrainEngine:
             self.optimizer_step()
         nnops.accum_advance(self._acc_state, self.grad_accum)
 
+    def _adam(self, p, g, m, v, vmax, shadow, flat_range=None, aux_name=None):
+        """The engine's one Adam launch: elements [a, b) = flat_range of the flat buffer, or the aux parameter aux_name."""
+        b1, b2 = self.betas
+        fp8 = None
+        if flat_range is not None and self.fp8 and self._w8_in_adam:
+            a, b = flat_range
+            if a % 8 or b % 8:           # (segments and chunk cuts are multiples of 16: cannot happen; a silent fallback would
+                raise KvqError(f"TrainEngine: Adam range [{a}, {b}) is not 8-aligned")       # leave the fp8 mirror stale)
+            fp8 = (*self._w8_adam, a)    # the update also writes the fp8 mirror of the GEMM weights in [a, b) (scales of the last refresh)
+        if self._pg is None:
+            nnops.adam_step_dev(p, g, m, v, self._state, b1, b2, self.eps, self.wd, vmax=vmax, shadow=shadow, guard=self._guard, fp8=fp8)
+            return
+        # parameter groups: still ONE launch.  An aux parameter, or a range whose blocks share a group j, passes no block table (the
+        # work of adam_step_dev); any other range looks its groups up per 16-element block of the flat buffer, indexed from element a.
+        pg = self._pg
+        if aux_name is not None:
+            j = pg["group_of"][aux_name]
+        else:
+            if flat_range not in pg["range_group"]:
+                pg["range_group"][flat_range] = range_group(pg["blocks_host"], *flat_range)
+            j = pg["range_group"][flat_range]
+        one = slice(None) if j is None else slice(j, j + 1)
+        nnops.adam_step_grouped(p, g, m, v, self._state, b1, b2, self.eps, self.wd, vmax=vmax, shadow=shadow, guard=self._guard,
+                                block_group=pg["blocks"] if j is None else None, first_element=0 if flat_range is None else flat_range[0],
+                                group_lr_scale=pg["scale"][one], group_wd=pg["wd"][one],
+                                n_groups=len(pg["table"]) if j is None else 1, decoupled=self.decoupled_wd)
+
     def _adam_ranges(self, lo, hi):
         fl = self.flat
-        b1, b2 = self.betas
         grad = self._grad_src()
         for (a, b) in fl.ranges:
             a, b = max(a, lo), min(b, hi)
-            if a < b and self.fp8 and self._w8_in_adam:
-                if a % 8 or b % 8:           # (segments and chunk cuts are multiples of 16: cannot happen; a silent fallback would
-                    raise KvqError(f"TrainEngine: Adam range [{a}, {b}) is not 8-aligned")       # leave the fp8 mirror stale)
-                # the update also writes the fp8 mirror of the GEMM weights in [a, b) (scales of the last refresh)
-                args = (fl.master[a:b].data_ptr(), grad[a:b].data_ptr(), fl.m[a:b].data_ptr(), fl.v[a:b].data_ptr(),
-                        fl.vmax[a:b].data_ptr() if fl.vmax is not None else None, fl.shadow[a:b].data_ptr(), b - a,
-                        nnops.io_dtype_of(grad), self._state.data_ptr(), b1, b2, self.eps, self.wd, 1.0,
-                        self._w8.data_ptr(), self._w8_span.data_ptr(), self._w8_scale.data_ptr(),
-                        self._w8_off.data_ptr(), self._w8_n.data_ptr(), len(self._w8_index), a)
-                if self._guard is not None:
-                    check(lib().kvq_adam_step_guarded_fp8(*args, self._guard.data_ptr(), stream_ptr()), "kvq_adam_step_guarded_fp8")
-                else:
-                    check(lib().kvq_adam_step_dev_fp8(*args, stream_ptr()), "kvq_adam_step_dev_fp8")
-            elif a < b and self._pg is not None:
-                # parameter groups: still ONE launch per range.  A range whose blocks share a group passes no block table (the work of
-                # adam_step_dev); any other looks its groups up per 16-element block of the flat buffer, indexed from element a.
-                pg = self._pg
-                if (a, b) not in pg["range_group"]:
-                    pg["range_group"][(a, b)] = range_group(pg["blocks_host"], a, b)
-                j = pg["range_group"][(a, b)]
-                nnops.adam_step_grouped(fl.master[a:b], grad[a:b], fl.m[a:b], fl.v[a:b], self._state, b1, b2, self.eps, self.wd,
-                                        vmax=fl.vmax[a:b] if fl.vmax is not None else None,
-                                        shadow=fl.shadow[a:b] if fl.shadow is not fl.master else None, guard=self._guard,
-                                        block_group=pg["blocks"] if j is None else None, first_element=a,
-                                        group_lr_scale=pg["scale"] if j is None else pg["scale"][j:j + 1],
-                                        group_wd=pg["wd"] if j is None else pg["wd"][j:j + 1],
-                                        n_groups=len(pg["table"]) if j is None else 1, decoupled=self.decoupled_wd)
-            elif a < b:
-                nnops.adam_step_dev(fl.master[a:b], grad[a:b], fl.m[a:b], fl.v[a:b], self._state, b1, b2, self.eps, self.wd,
-                                    vmax=fl.vmax[a:b] if fl.vmax is not None else None,
-                                    shadow=fl.shadow[a:b] if fl.shadow is not fl.master else None, guard=self._guard)
+            if a < b:
+                self._adam(fl.master[a:b], grad[a:b], fl.m[a:b], fl.v[a:b], fl.vmax[a:b] if fl.vmax is not None else None,
+                           fl.shadow[a:b] if fl.shadow is not fl.master else None, flat_range=(a, b))
 
     def optimizer_step(self):
         self._wema_refuse("optimizer_step")
@@ -2767,28 +2766,16 @@ class TrainEngine:
         self._after_update()
 
     def _advance_state(self):
-        """step += 1, lr and bias corrections of the step on the device; the _sched entry only when a schedule option is on."""
-        b1, b2 = self.betas
-        if self.lr_schedule is None:
-            nnops.step_state_advance(self._state, self.lr, self.gamma, self.milestones, b1, b2)
-            return
-        W, kind, T, r = self.lr_schedule
-        nnops.step_state_advance_sched(self._state, self.lr, self.gamma, self.milestones, b1, b2, warmup_steps=W,
+        """step += 1, lr and bias corrections of the step on the device; without a schedule option the neutral schedule."""
+        W, kind, T, r = self.lr_schedule or (0, "none", 0, 0.0)
+        nnops.step_state_advance_sched(self._state, self.lr, self.gamma, self.milestones, *self.betas, warmup_steps=W,
                                        decay_kind=nnops.LR_DECAY_KINDS[kind], total_steps=T, min_ratio=r)
 
     def _adam_aux(self):
-        b1, b2 = self.betas
         for a in self.aux:
-            if a["p"].requires_grad and self._pg is not None:         # the one-group form with the aux parameter's group
-                j = self._pg["group_of"][a["name"]]
-                nnops.adam_step_grouped(a["p"].data.view(-1), a[self._aux_src].view(-1), a["m"].view(-1), a["v"].view(-1), self._state,
-                                        b1, b2, self.eps, self.wd, vmax=a["vmax"].view(-1) if a["vmax"] is not None else None,
-                                        guard=self._guard, group_lr_scale=self._pg["scale"][j:j + 1], group_wd=self._pg["wd"][j:j + 1],
-                                        n_groups=1, decoupled=self.decoupled_wd)
-            elif a["p"].requires_grad:
-                nnops.adam_step_dev(a["p"].data.view(-1), a[self._aux_src].view(-1), a["m"].view(-1), a["v"].view(-1), self._state,
-                                    b1, b2, self.eps, self.wd, vmax=a["vmax"].view(-1) if a["vmax"] is not None else None,
-                                    guard=self._guard)
+            if a["p"].requires_grad:
+                self._adam(a["p"].data.view(-1), a[self._aux_src].view(-1), a["m"].view(-1), a["v"].view(-1),
+                           a["vmax"].view(-1) if a["vmax"] is not None else None, None, aux_name=a["name"])
 
     def _after_update(self):
         if self.vq_kind in ("VectorQuantizer", "MultiVectorQuantizer") and (self.E.requires_grad or self.revive_after is not None):

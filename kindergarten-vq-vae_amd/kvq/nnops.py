@@ -334,24 +334,36 @@ def attn_bwd(q, k, v, mask, g_ctx, B, nh, Sq, Sk, causal, p_drop, seed, site, g_
                              _p(bias_part_v), int(ldp_q), int(ldp_kv), stream_ptr()), "kvq_attn_bwd")
 
 
+def _adam_args(p32, g, m, v, vmax, shadow, step_state, beta1, beta2, eps, weight_decay, grad_scale):
+    """What every kvq_adam_step* entry starts with (kvq_adam_step has lr where the others have the step state)."""
+    return (p32.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(vmax), _p(shadow), p32.numel(), io_dtype_of(g), _p(step_state),
+            float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale))
+
+
+def _adam_call(name, guarded_name, args, guard):
+    """One Adam entry, or with a gradient guard its guarded form, which takes the guard state last."""
+    if guard is not None:
+        name, args = guarded_name, args + (_guard_ptr(guard),)
+    check(getattr(lib(), name)(*args, stream_ptr()), name)
+
+
 def adam_step(p32, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, vmax=None, shadow=None, grad_scale=1.0):
-    check(lib().kvq_adam_step(p32.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(vmax), _p(shadow), p32.numel(),
-                              io_dtype_of(g), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
-                              float(grad_scale), stream_ptr()), "kvq_adam_step")
+    a = _adam_args(p32, g, m, v, vmax, shadow, None, beta1, beta2, eps, weight_decay, grad_scale)
+    check(lib().kvq_adam_step(*a[:8], float(lr), *a[9:13], int(step), a[13], stream_ptr()), "kvq_adam_step")
 
 
 def adam_step_dev(p32, g, m, v, step_state, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, vmax=None, shadow=None, grad_scale=1.0,
-                  guard=None):
+                  guard=None, fp8=None):
     """adam_step with lr and the bias corrections read on the device from `step_state` (see step_state_advance).  guard: a gradient
-    guard state (new_grad_guard): the gradient is scaled by grad_scale * guard.coef, and nothing is stored when guard.skip is set."""
-    if guard is not None:
-        check(lib().kvq_adam_step_guarded(p32.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(vmax), _p(shadow), p32.numel(),
-                                          io_dtype_of(g), step_state.data_ptr(), float(beta1), float(beta2), float(eps),
-                                          float(weight_decay), float(grad_scale), _guard_ptr(guard), stream_ptr()), "kvq_adam_step_guarded")
-        return
-    check(lib().kvq_adam_step_dev(p32.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(vmax), _p(shadow), p32.numel(),
-                                  io_dtype_of(g), step_state.data_ptr(), float(beta1), float(beta2), float(eps), float(weight_decay),
-                                  float(grad_scale), stream_ptr()), "kvq_adam_step_dev")
+    guard state (new_grad_guard): the gradient is scaled by grad_scale * guard.coef, and nothing is stored when guard.skip is set.
+    fp8: (mirror, span_segment, seg_scale, seg_off, seg_n, nseg, first_element) of kvq_adam_step_dev_fp8 (include/kvq.h): the update
+    also writes the fp8 mirror of the GEMM weights among its elements."""
+    args = _adam_args(p32, g, m, v, vmax, shadow, step_state, beta1, beta2, eps, weight_decay, grad_scale)
+    if fp8 is None:
+        return _adam_call("kvq_adam_step_dev", "kvq_adam_step_guarded", args, guard)
+    *tables, nseg, first_element = fp8
+    _adam_call("kvq_adam_step_dev_fp8", "kvq_adam_step_guarded_fp8",
+               args + tuple(t.data_ptr() for t in tables) + (int(nseg), int(first_element)), guard)
 
 
 def new_step_state(device):
@@ -359,13 +371,16 @@ def new_step_state(device):
     return torch.zeros(3, dtype=torch.int64, device=device)
 
 
-def step_state_advance(step_state, lr0, gamma, milestones, beta1, beta2):
-    """step += 1 and the lr / bias corrections of that step."""
+def _step_state_args(step_state, lr0, gamma, milestones, beta1, beta2):
     import ctypes
     ms = [int(x) for x in milestones]
-    arr = (ctypes.c_int64 * max(len(ms), 1))(*ms)
-    check(lib().kvq_step_state_advance(step_state.data_ptr(), float(lr0), float(gamma), arr, len(ms), float(beta1), float(beta2),
-                                       stream_ptr()), "kvq_step_state_advance")
+    return (step_state.data_ptr(), float(lr0), float(gamma), (ctypes.c_int64 * max(len(ms), 1))(*ms), len(ms), float(beta1), float(beta2))
+
+
+def step_state_advance(step_state, lr0, gamma, milestones, beta1, beta2):
+    """step += 1 and the lr / bias corrections of that step."""
+    check(lib().kvq_step_state_advance(*_step_state_args(step_state, lr0, gamma, milestones, beta1, beta2), stream_ptr()),
+          "kvq_step_state_advance")
 
 
 LR_DECAY_KINDS = {"none": 0, "linear": 1, "cosine": 2}       # decay_kind of kvq_step_state_advance_sched
@@ -374,11 +389,8 @@ LR_DECAY_KINDS = {"none": 0, "linear": 1, "cosine": 2}       # decay_kind of kvq
 def step_state_advance_sched(step_state, lr0, gamma, milestones, beta1, beta2, warmup_steps=0, decay_kind=0, total_steps=0, min_ratio=0.0):
     """step_state_advance with a linear warm-up over `warmup_steps` steps and a linear (1) / cosine (2) decay to min_ratio * lr0 at
     `total_steps` (include/kvq.h); warmup_steps 0 and decay_kind 0 give step_state_advance's bits."""
-    import ctypes
-    ms = [int(x) for x in milestones]
-    arr = (ctypes.c_int64 * max(len(ms), 1))(*ms)
-    check(lib().kvq_step_state_advance_sched(step_state.data_ptr(), float(lr0), float(gamma), arr, len(ms), float(beta1), float(beta2),
-                                             int(warmup_steps), int(decay_kind), int(total_steps), float(min_ratio), stream_ptr()),
+    check(lib().kvq_step_state_advance_sched(*_step_state_args(step_state, lr0, gamma, milestones, beta1, beta2), int(warmup_steps),
+                                             int(decay_kind), int(total_steps), float(min_ratio), stream_ptr()),
           "kvq_step_state_advance_sched")
 
 
@@ -398,13 +410,9 @@ def adam_step_grouped(p32, g, m, v, step_state, beta1=0.9, beta2=0.999, eps=1e-8
     for t in (group_lr_scale, group_wd):
         if t is not None and t.numel() < n_groups:
             raise KvqError(f"adam_step_grouped: {n_groups} groups, a table of {t.numel()}")
-    args = (p32.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(vmax), _p(shadow), n, io_dtype_of(g), step_state.data_ptr(),
-            float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale), _p(block_group), int(first_element),
-            _p(group_lr_scale), _p(group_wd), int(n_groups), int(bool(decoupled)))
-    if guard is not None:
-        check(lib().kvq_adam_step_grouped_guarded(*args, _guard_ptr(guard), stream_ptr()), "kvq_adam_step_grouped_guarded")
-        return
-    check(lib().kvq_adam_step_grouped(*args, stream_ptr()), "kvq_adam_step_grouped")
+    args = _adam_args(p32, g, m, v, vmax, shadow, step_state, beta1, beta2, eps, weight_decay, grad_scale)
+    _adam_call("kvq_adam_step_grouped", "kvq_adam_step_grouped_guarded",
+               args + (_p(block_group), int(first_element), _p(group_lr_scale), _p(group_wd), int(n_groups), int(bool(decoupled))), guard)
 
 
 def read_step_state(step_state):

@@ -1,5 +1,5 @@
 """f64 reference and judges for the grouped / decoupled Adam update and the learning-rate schedule (adam_group_kernel,
-step_state_advance_sched_kernel of csrc/kvq_nn.hip; include/kvq.h "parameter groups").  Built on tests/_adam_ref.py: the same input
+step_state_advance_sched_kernel of csrc/kvq_adam.hip; include/kvq.h "parameter groups").  Built on tests/_adam_ref.py: the same input
 generator, the same convention (every judge returns |kernel - reference| / bound per element, at most 1 passes) and the same kind
 of bound -- counted f32 roundings, each count beside its term, no constant fitted to a kernel's output.
 tests/test_adam_groups_ref.py shows on the CPU that the judges accept an op-by-op f32 restatement of the contract and reject

@@ -1,5 +1,5 @@
-"""f64 references, input generator and judges for the Adam kernels and the step state (adam_kernel, step_state_advance_kernel of
-csrc/kvq_nn.hip; tests/test_adam_parity_gpu.py).  Everything here is plain torch on whatever device its inputs live on (the CPU,
+"""f64 references, input generator and judges for the Adam kernels and the step state (adam_kernel, step_state_advance_sched_kernel of
+csrc/kvq_adam.hip; tests/test_adam_parity_gpu.py).  Everything here is plain torch on whatever device its inputs live on (the CPU,
 or the GPU in f64 for the grid-stride cases); tests/test_adam_ref.py shows on the CPU that each judge accepts an op-by-op f32
 restatement of the kernel and rejects planted mistakes.
 

@@ -1,5 +1,5 @@
 """Per-element parity of kvq_adam_step_grouped / _grouped_guarded (adam_group_kernel) and of kvq_step_state_advance_sched
-(csrc/kvq_nn.hip) against f64: the judges of tests/_adam_groups_ref.py (counted f32 roundings; tests/test_adam_groups_ref.py checks
+(csrc/kvq_adam.hip) against f64: the judges of tests/_adam_groups_ref.py (counted f32 roundings; tests/test_adam_groups_ref.py checks
 them on the CPU), the frames, states and tallies of tests/test_adam_parity_gpu.py."""
 import pytest
 import torch

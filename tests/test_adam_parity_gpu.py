@@ -1,5 +1,5 @@
 """Per-element parity of the Adam family (adam_kernel behind kvq_adam_step, _dev, _dev_fp8, _guarded, _guarded_fp8) and of
-kvq_step_state_advance (csrc/kvq_nn.hip) against f64.
+kvq_step_state_advance (csrc/kvq_adam.hip) against f64.
 
 One step from a random non-zero pre-state, every stored m', v', vmax', p' judged per element inside bounds that count f32
 roundings (tests/_adam_ref.py; tests/test_adam_ref.py checks the judges on the CPU); the bf16 shadow bitwise RNE of the stored

@@ -1,5 +1,5 @@
 """CPU self-check of tests/_adam_ref.py: the reference is torch.optim.Adam, every judge accepts an op-by-op numpy float32
-restatement of adam_update4 / step_state_advance_kernel (csrc/kvq_nn.hip) on the full input generator and rejects each planted
+restatement of adam_update4 / step_state_advance_sched_kernel (csrc/kvq_adam.hip) on the full input generator and rejects each planted
 mistake on the same inputs, and the generator stays clear of the denormals.  Measured figures: profiles/adam_parity.md."""
 import math
 
@@ -223,7 +223,7 @@ def test_generator_stays_clear_of_the_denormals():
 # step state
 # ---------------------------------------------------------------------------------------------------------------
 def restate_step_state(t, lr0, gamma, milestones, beta1, beta2, mistake=None):
-    """step_state_advance_kernel: f64 arithmetic on the f32 arguments, each field cast to f32 once."""
+    """step_state_advance_sched_kernel without a schedule: f64 arithmetic on the f32 arguments, each field cast to f32 once."""
     k = sum(1 for ms in milestones if ((t - 1 > ms) if mistake == "milestone >" else (t - 1 >= ms)))
     lr = np.float64(np.float32(lr0))
     for _ in range(k):

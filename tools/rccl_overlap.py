@@ -42,7 +42,7 @@ def main():
     rows = load(sys.argv[1])
     spans = steps_of(rows)
     if not spans:
-        raise SystemExit("no steps found (step_state_advance_kernel marks the step boundary)")
+        raise SystemExit("no steps found (step_state_advance_sched_kernel marks the step boundary)")
     coll_t = comp = 0
     by = collections.defaultdict(lambda: {"alone": [], "beside": []})
     walls = []
