@@ -249,6 +249,16 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
     return v;
 }
 
+// ---- the final sum of f32 partial rows (column sums of csrc/kvq_nn.hip, LayerNorm partials of csrc/kvq_ln.hip) is the one-item
+//      case of the batched reduction: same kernel, same summation order
+static inline int colsum_f32_partials(const float* part, int64_t P, int64_t C, int64_t ldp, void* out, int out_dtype, float scale,
+                                      int accumulate, hipStream_t st) {
+    kvq_reduce_item it = {};
+    it.src = part; it.dst = out; it.count = P; it.cols = C; it.ld = ldp; it.scale = scale;
+    it.src_dtype = KVQ_F32; it.dst_dtype = out_dtype; it.accumulate = accumulate;
+    return kvq_reduce_batch(&it, 1, st);
+}
+
 // ---- gradient guard state (include/kvq.h): written by kvq_grad_guard_finalize (csrc/kvq_gradnorm.hip), read by adam_kernel -----
 struct GradGuard {
     double sumsq;                 // sum of squares of the step's gradient

@@ -16,7 +16,7 @@
 namespace kvq {
 
 constexpr int Q_THREADS = 256;
-// (FP8_MAX, amax8, quant8, fp8_amax_note: kvq_common.h -- the producers of csrc/kvq_nn.hip / kvq_gemm2.hip emit the same bytes)
+// (FP8_MAX, amax8, quant8, fp8_amax_note: kvq_common.h -- the producers of csrc/kvq_ln.hip / kvq_nn.hip / kvq_gemm2.hip emit the same bytes)
 
 __device__ __forceinline__ void block_amax_to(float m, float* dst) {
     __shared__ float sm[Q_THREADS / WAVE];

@@ -66,7 +66,7 @@ struct Problem {
     const float* scaleA;               // fp8 kernel: per-tensor quantisation scales of the two operands (device scalars)
     const float* scaleB;
     // EPI_DROPRES: C = dropout(A.B + bias) + R, R = H ([M, N], row stride ldc) -- the input of the LayerNorm behind a BertSelfOutput /
-    // BertOutput dense (modeling_bert.py:282-296, 339-352), with the masks of csrc/kvq_nn.hip's drln kernels (same Philox stream)
+    // BertOutput dense (modeling_bert.py:282-296, 339-352), with the masks of csrc/kvq_ln.hip's drln kernels (same Philox stream)
     unsigned long long seed;
     const unsigned long long* seed_off;
     unsigned site, thresh;

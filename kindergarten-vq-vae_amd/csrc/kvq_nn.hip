@@ -1,15 +1,14 @@
 // kvq_nn.hip -- the memory-bound pieces of the BERT encoder/decoder blocks of the training step, fused for gfx950.
 //
 // The reference runs these as separate ATen ops inside HuggingFace's BertLayer (modeling_bert.py:139-352): bias add,
-// dropout, residual add, LayerNorm, GELU and softmax attention.  Here each block boundary is one
-// kernel pass over the activations (bf16 storage, f32 arithmetic):
-//   kvq_dropout_residual_ln_{fwd,bwd}   BertSelfOutput / BertOutput (:282-293, :340-352): LN(dropout(y) + residual)
+// dropout, GELU and softmax attention.  Here each is one kernel pass over the activations (bf16 storage, f32 arithmetic):
 //   kvq_gelu_{fwd,bwd}                   BertIntermediate activation (:325-337), erf form
-//   kvq_colsum                           bias gradients (sum over tokens)
+//   kvq_colsum, kvq_reduce_batch         bias gradients (sum over tokens), the final sum of partial rows
 //   kvq_attn_{fwd,bwd}                   BertSelfAttention / BertCrossAttention core (:111-204) for sentences of <= 32 tokens:
 //                                        one wave per (sentence, head), scores never leave registers / LDS
+// plus dropout, the embedding gradient and Gumbel-softmax.  (The LayerNorm family is csrc/kvq_ln.hip.)
 // Dropout masks are never stored: both directions regenerate them from a counter-based generator (Philox4x32-10)
-// keyed by (seed, site) and indexed by the element position.
+// keyed by (seed, site) and indexed by the element position; kvq_set_seed_offset keeps the per-thread addend of every seed here.
 #include <math.h>
 
 #include <stdlib.h>
@@ -20,481 +19,6 @@
 namespace kvq {
 
 // (Philox4x32-10, drop_bits, keep_scale, drop_threshold: kvq_common.h -- the GEMM epilogue of csrc/kvq_gemm2.hip draws the same masks)
-
-// ---------------------------------------------------------------------------------------------------------------
-// LN(dropout(y) + residual): one wave per row, rows of H <= 4096 (H % 4 == 0); bf16 or f32 io
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int LN_MAX_PER_LANE = 16;   // H <= 64 * 4 * 16 = 4096
-
-// RES = false (round 5): no residual operand at all -- the LayerNorm-only pass behind kvq_gemm_bf16_dropres, whose GEMM epilogue
-// already added the residual: one load stream instead of two.
-template <int DT, int PER, bool RES = true>
-__global__ __launch_bounds__(256) void drln_fwd_kernel(const void* __restrict__ y, const void* __restrict__ resid,
-                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        int64_t N, int H, float eps, float p_drop, unsigned thresh,
-                                                        unsigned long long seed, const unsigned long long* __restrict__ seed_off,
-                                                        unsigned site, void* __restrict__ out,
-                                                        void* __restrict__ pre, float* __restrict__ mean_out,
-                                                        float* __restrict__ rstd_out, unsigned char* __restrict__ out8 = nullptr,
-                                                        float* __restrict__ st8 = nullptr) {
-    // out8 / st8 (round 5, bf16 io only): also the fp8 (e4m3) copy of `out` for the fp8 GEMM that reads it next -- the bytes
-    // kvq_fp8_quantize_delayed(out) would write (this site's scale of the previous step, this call's amax noted in its state)
-    // EVERY load of the row is requested before anything is done with one of them, and no load sits behind a branch: chunk
-    // indices past the row are clamped (and masked out of the sums), a missing residual reads y again and is weighted 0.
-    // As first written ("if (c < nchunk) { load y; ...; if (resid) load resid; ... }" per chunk) hipcc put s_waitcnt vmcnt(0)
-    // behind each load: six dependent trips to memory per row, then three more for gamma / beta -- 13.3 us for the 50 MB of a
-    // [8192, 768] call, one round of waves doing nothing but waiting (ISA audit of round 3, profiles/NOTES_r01-r03_design_and_experiments.md section 2.5).
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= N) return;
-    const int nchunk = H >> 2;
-    const float inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
-    const void* rp = resid ? resid : y;
-    const float rw = resid ? 1.0f : 0.0f;
-    constexpr bool EARLY_GB = PER <= 4;        // (wide rows: gamma / beta stay L2-resident small loads of the last pass)
-    f32x4 v[PER], r[RES ? PER : 1], g[EARLY_GB ? PER : 1], b[EARLY_GB ? PER : 1];
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        const int c = lane + WAVE * t < nchunk ? lane + WAVE * t : nchunk - 1;
-        const size_t off = (size_t)row * H + 4 * c;
-        v[t] = IO<DT>::load4(y, off);
-        if constexpr (RES) r[t] = IO<DT>::load4(rp, off);
-    }
-    if constexpr (EARLY_GB) {
-#pragma unroll
-        for (int t = 0; t < PER; ++t) {
-            const int c = lane + WAVE * t < nchunk ? lane + WAVE * t : nchunk - 1;
-            g[t] = *reinterpret_cast<const f32x4*>(gamma + 4 * c);
-            b[t] = *reinterpret_cast<const f32x4*>(beta + 4 * c);
-        }
-    }
-    if (seed_off) seed += *seed_off;          // device-resident step counter (a captured graph replays with fresh masks): the
-                                              // dependent scalar load waits while the row is on its way
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        const int c = lane + WAVE * t;
-        f32x4 a = v[t];
-        if (p_drop > 0.f) {                   // (uniform; arithmetic only: the Philox rounds run while the loads are in flight)
-            const U4 kb = drop_bits(seed, site, (unsigned long long)row * nchunk + c);
-            a.x *= keep_scale(kb.x, thresh, inv_keep); a.y *= keep_scale(kb.y, thresh, inv_keep);
-            a.z *= keep_scale(kb.z, thresh, inv_keep); a.w *= keep_scale(kb.w, thresh, inv_keep);
-        }
-        if constexpr (RES) a += r[t] * rw;
-        // LayerNorm sees the STORED pre-activation (bf16-rounded when io is bf16): backward re-reads exactly that
-        a.x = IO<DT>::round(a.x); a.y = IO<DT>::round(a.y); a.z = IO<DT>::round(a.z); a.w = IO<DT>::round(a.w);
-        if (c < nchunk) {
-            if (pre) IO<DT>::store4(pre, (size_t)row * H + 4 * c, a);
-            sum += (a.x + a.y) + (a.z + a.w);
-        }
-        v[t] = a;
-    }
-    const float mean = wave_sum_f32(sum) / (float)H;
-    float sq = 0.f;
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        if (lane + WAVE * t < nchunk) {
-            const f32x4 d = v[t] - mean;
-            sq += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-        }
-    }
-    const float var = wave_sum_f32(sq) / (float)H;
-    const float rstd = rsqrtf(var + eps);
-    const float s8 = (DT == KVQ_BF16 && out8) ? st8[0] : 1.0f;
-    float am8 = 0.f;
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        const int c = lane + WAVE * t;
-        if (c < nchunk) {
-            f32x4 gg, bb;
-            if constexpr (EARLY_GB) { gg = g[t]; bb = b[t]; }
-            else { gg = *reinterpret_cast<const f32x4*>(gamma + 4 * c); bb = *reinterpret_cast<const f32x4*>(beta + 4 * c); }
-            const f32x4 o = (v[t] - mean) * rstd * gg + bb;
-            IO<DT>::store4(out, (size_t)row * H + 4 * c, o);
-            if (DT == KVQ_BF16 && out8) {                     // (uniform)
-                const f32x4 ob = {IO<DT>::round(o.x), IO<DT>::round(o.y), IO<DT>::round(o.z), IO<DT>::round(o.w)};
-                am8 = fmaxf(am8, amax4(ob));
-                *reinterpret_cast<unsigned*>(out8 + (size_t)row * H + 4 * c) = quant4(ob, s8);
-            }
-        }
-    }
-    if (DT == KVQ_BF16 && out8) fp8_amax_note(am8, st8, (unsigned)row);
-    if (lane == 0) {
-        if (mean_out) mean_out[row] = mean;
-        if (rstd_out) rstd_out[row] = rstd;
-    }
-}
-
-// BertEmbeddings (modeling_bert.py:53-110) in one pass: out = dropout(LayerNorm(word[ids[n]] + (pos[n % S] + type[0]))).
-// Replaces F.embedding + the position/type add + its repeat over the batch + the LayerNorm kernel + the dropout kernel (five
-// launches, three [N, H] round trips).  Rounding as those kernels rounded: pos + type to the io dtype, the sum to the io dtype
-// (= `pre`, what backward re-reads), the LayerNorm output to the io dtype BEFORE the keep scale.  One wave per row.
-template <int DT, int PER>
-__global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __restrict__ ids, const void* __restrict__ word,
-                                                            const void* __restrict__ pos, const void* __restrict__ type_row,
-                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            int64_t N, int S, int H, int64_t V, float eps, float p_drop, unsigned thresh,
-                                                            unsigned long long seed, const unsigned long long* __restrict__ seed_off,
-                                                            unsigned site, void* __restrict__ out, void* __restrict__ pre,
-                                                            float* __restrict__ mean_out, float* __restrict__ rstd_out) {
-    if (seed_off) seed += *seed_off;
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= N) return;
-    const int nchunk = H >> 2;
-    int64_t id = ids[row];
-    id = id < 0 ? 0 : (id >= V ? V - 1 : id);                 // (torch raises on an id outside the table; the kernel must not fault)
-    const int ps = (int)(row % S);
-    const float inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
-    f32x4 v[PER];
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        const int c = lane + WAVE * t;
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        if (c < nchunk) {
-            f32x4 pt = IO<DT>::load4(pos, (size_t)ps * H + 4 * c) + IO<DT>::load4(type_row, 4 * c);
-            pt.x = IO<DT>::round(pt.x); pt.y = IO<DT>::round(pt.y); pt.z = IO<DT>::round(pt.z); pt.w = IO<DT>::round(pt.w);
-            a = IO<DT>::load4(word, (size_t)id * H + 4 * c) + pt;
-            a.x = IO<DT>::round(a.x); a.y = IO<DT>::round(a.y); a.z = IO<DT>::round(a.z); a.w = IO<DT>::round(a.w);
-            if (pre) IO<DT>::store4(pre, (size_t)row * H + 4 * c, a);
-            sum += (a.x + a.y) + (a.z + a.w);
-        }
-        v[t] = a;
-    }
-    const float mean = wave_sum_f32(sum) / (float)H;
-    float sq = 0.f;
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        if (lane + WAVE * t < nchunk) {
-            const f32x4 d = v[t] - mean;
-            sq += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-        }
-    }
-    const float var = wave_sum_f32(sq) / (float)H;
-    const float rstd = rsqrtf(var + eps);
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        const int c = lane + WAVE * t;
-        if (c < nchunk) {
-            const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 4 * c);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(beta + 4 * c);
-            f32x4 o = (v[t] - mean) * rstd * g + b;
-            if (p_drop > 0.f) {
-                const U4 kb = drop_bits(seed, site, (unsigned long long)row * nchunk + c);
-                o.x = IO<DT>::round(o.x) * keep_scale(kb.x, thresh, inv_keep); o.y = IO<DT>::round(o.y) * keep_scale(kb.y, thresh, inv_keep);
-                o.z = IO<DT>::round(o.z) * keep_scale(kb.z, thresh, inv_keep); o.w = IO<DT>::round(o.w) * keep_scale(kb.w, thresh, inv_keep);
-            }
-            IO<DT>::store4(out, (size_t)row * H + 4 * c, o);
-        }
-    }
-    if (lane == 0) {
-        if (mean_out) mean_out[row] = mean;
-        if (rstd_out) rstd_out[row] = rstd;
-    }
-}
-
-// backward: g_pre = rstd * (g*gamma - mean(g*gamma) - xhat * mean(g*gamma*xhat));  g_resid = g_pre;
-//           g_y = g_pre * dropout_mask/(1-p);  dgamma/dbeta partials per workgroup (summed by colsum_final_kernel)
-constexpr int LNB_ROWS = 16;   // rows per workgroup (4 waves x 4 rows, all in flight at once): 512 workgroups and 512 partial rows at N = 8192
-
-template <int DT, int PER>
-__global__ __launch_bounds__(256) void drln_bwd_kernel(const void* __restrict__ g_out, const void* __restrict__ pre,
-                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                        const float* __restrict__ gamma, int64_t N, int H, float p_drop,
-                                                        unsigned thresh, unsigned long long seed,
-                                                        const unsigned long long* __restrict__ seed_off, unsigned site,
-                                                        void* __restrict__ g_y, void* __restrict__ g_resid,
-                                                        float* __restrict__ part_dgamma, int want_dbias, int drop_on_out) {
-    // drop_on_out: the block is dropout(LayerNorm(.)) (BertEmbeddings) instead of LayerNorm(dropout(y) + resid): the mask of
-    // (seed, site) then applies to the incoming gradient g_out (rounded to the io dtype, as the separate kernel stored it)
-    extern __shared__ __attribute__((aligned(16))) float lds[];   // [4 waves][3][H]
-    if (seed_off) seed += *seed_off;
-    constexpr int RW = LNB_ROWS / 4;                              // rows per wave
-    constexpr int RF = PER <= 4 ? RW : 1;                         // ... of which RF are in flight at once (register budget)
-    typedef typename std::conditional<(PER > 8), unsigned long long, unsigned>::type KeepBits;   // 4 bits per chunk
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nchunk = H >> 2;
-    const float inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
-    f32x4 dg[PER], db[PER], dy[PER], gm[PER];     // dy: column sums of g_y = bias gradient of the dense layer in front
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        dg[t] = 0.f; db[t] = 0.f; dy[t] = 0.f;
-        const int c = lane + WAVE * t < nchunk ? lane + WAVE * t : nchunk - 1;
-        gm[t] = *reinterpret_cast<const f32x4*>(gamma + 4 * c);
-    }
-#pragma unroll
-    for (int rb = 0; rb < RW; rb += RF) {
-        const int64_t row0 = (int64_t)blockIdx.x * LNB_ROWS + w * RW + rb;
-        if (row0 >= N) break;                                     // wave-uniform
-        // 1. every load of these rows goes out first (rows past N are clamped and weighted 0: no branch around a load)
-        f32x4 go[RF][PER], x[RF][PER];
-        float mu[RF], rs[RF], live[RF];
-#pragma unroll
-        for (int r = 0; r < RF; ++r) {
-            const int64_t row = row0 + r < N ? row0 + r : N - 1;
-            live[r] = row0 + r < N ? 1.0f : 0.0f;
-            mu[r] = mean[row]; rs[r] = rstd[row];
-#pragma unroll
-            for (int t = 0; t < PER; ++t) {
-                const int c = lane + WAVE * t < nchunk ? lane + WAVE * t : nchunk - 1;
-                const size_t off = (size_t)row * H + 4 * c;
-                go[r][t] = IO<DT>::load4(g_out, off);
-                x[r][t] = IO<DT>::load4(pre, off);
-            }
-        }
-        // 2. the dropout keep bits do not depend on the loads: Philox runs while they are in flight
-        KeepBits keepbits[RF];
-#pragma unroll
-        for (int r = 0; r < RF; ++r) {
-            keepbits[r] = ~(KeepBits)0;
-            if ((g_y || drop_on_out) && p_drop > 0.f) {
-                KeepBits kb = 0;
-#pragma unroll
-                for (int t = 0; t < PER; ++t) {
-                    const int c = lane + WAVE * t;
-                    const U4 b = drop_bits(seed, site, (unsigned long long)(row0 + r) * nchunk + c);
-                    kb |= (KeepBits)((b.x >= thresh ? 1u : 0u) | (b.y >= thresh ? 2u : 0u) | (b.z >= thresh ? 4u : 0u) | (b.w >= thresh ? 8u : 0u)) << (4 * t);
-                }
-                keepbits[r] = kb;
-            }
-        }
-        // 3. row statistics of all rows in flight, then their outputs
-        float s1[RF], s2[RF];
-#pragma unroll
-        for (int r = 0; r < RF; ++r) {
-            float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int t = 0; t < PER; ++t) {
-                const float m = (lane + WAVE * t < nchunk) ? live[r] : 0.0f;
-                f32x4 g = go[r][t] * m;
-                if (drop_on_out) {
-                    const unsigned kb = (unsigned)(keepbits[r] >> (4 * t));
-                    g.x = IO<DT>::round(g.x * ((kb & 1u) ? inv_keep : 0.f)); g.y = IO<DT>::round(g.y * ((kb & 2u) ? inv_keep : 0.f));
-                    g.z = IO<DT>::round(g.z * ((kb & 4u) ? inv_keep : 0.f)); g.w = IO<DT>::round(g.w * ((kb & 8u) ? inv_keep : 0.f));
-                }
-                const f32x4 xh = (x[r][t] - mu[r]) * rs[r];
-                const f32x4 tt = g * gm[t];
-                dg[t] += g * xh;
-                db[t] += g;
-                a1 += (tt.x + tt.y) + (tt.z + tt.w);
-                a2 += (tt.x * xh.x + tt.y * xh.y) + (tt.z * xh.z + tt.w * xh.w);
-                go[r][t] = tt; x[r][t] = xh;
-            }
-            s1[r] = a1; s2[r] = a2;
-        }
-#pragma unroll
-        for (int r = 0; r < RF; ++r) {
-            s1[r] = wave_sum_f32(s1[r]) / (float)H;
-            s2[r] = wave_sum_f32(s2[r]) / (float)H;
-        }
-#pragma unroll
-        for (int r = 0; r < RF; ++r) {
-            if (row0 + r >= N) break;                   // wave-uniform; only stores below
-#pragma unroll
-            for (int t = 0; t < PER; ++t) {
-                const int c = lane + WAVE * t;
-                if (c < nchunk) {
-                    const size_t off = (size_t)(row0 + r) * H + 4 * c;
-                    f32x4 gp = (go[r][t] - s1[r] - x[r][t] * s2[r]) * rs[r];
-                    if (g_resid) IO<DT>::store4(g_resid, off, gp);
-                    if (g_y) {
-                        if (!drop_on_out) {
-                            const unsigned kb = (unsigned)(keepbits[r] >> (4 * t));
-                            gp.x *= (kb & 1u) ? inv_keep : 0.f; gp.y *= (kb & 2u) ? inv_keep : 0.f;
-                            gp.z *= (kb & 4u) ? inv_keep : 0.f; gp.w *= (kb & 8u) ? inv_keep : 0.f;
-                        }
-                        IO<DT>::store4(g_y, off, gp);
-                        // what the consumer of g_y reads back is the STORED (possibly bf16-rounded) value
-                        dy[t].x += IO<DT>::round(gp.x); dy[t].y += IO<DT>::round(gp.y);
-                        dy[t].z += IO<DT>::round(gp.z); dy[t].w += IO<DT>::round(gp.w);
-                    }
-                }
-            }
-        }
-    }
-    float* l_dy = lds + (size_t)w * 3 * H;
-    float* l_dg = l_dy + H;
-    float* l_db = l_dg + H;
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        const int c = lane + WAVE * t;
-        if (c < nchunk) {
-            *reinterpret_cast<f32x4*>(l_dy + 4 * c) = dy[t];
-            *reinterpret_cast<f32x4*>(l_dg + 4 * c) = dg[t];
-            *reinterpret_cast<f32x4*>(l_db + 4 * c) = db[t];
-        }
-    }
-    __syncthreads();
-    // partial row layout: [dbias_prev(H) | dgamma(H) | dbeta(H)]
-    for (int j = threadIdx.x; j < 3 * H; j += 256) {
-        if (j < H && !want_dbias) continue;
-        float a = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < 4; ++ww) a += lds[(size_t)ww * 3 * H + j];
-        part_dgamma[(size_t)blockIdx.x * 3 * H + j] = a;
-    }
-}
-
-__device__ __forceinline__ float half_wave_sum_f32(float v) {
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m, WAVE);
-    return v;
-}
-
-
-// bf16 io, H % 8 == 0, H <= 8 * 32 * PER: HALF a wave per row, 16 bytes (8 elements) per lane and access instead of 8; LNB_ROWS rows
-// per workgroup = 2 per half wave, both in flight.  Same partial-row layout and the same dropout stream (one Philox call per 4
-// elements, indexed row * H/4 + chunk) as drln_bwd_kernel.  In the step: 16.7 -> 14.3 us per [8192, 768] call.  (The forward
-// kernel rebuilt the same way measured 13.3 against 13.4 us and was dropped again: it is not the access width that holds it.)
-template <int PER>
-__global__ __launch_bounds__(256) void drln_bwd16_kernel(const void* __restrict__ g_out, const void* __restrict__ pre,
-                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                          const float* __restrict__ gamma, int64_t N, int H, float p_drop,
-                                                          unsigned thresh, unsigned long long seed,
-                                                          const unsigned long long* __restrict__ seed_off, unsigned site,
-                                                          void* __restrict__ g_y, void* __restrict__ g_resid,
-                                                          float* __restrict__ part_dgamma, int want_dbias, int drop_on_out) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];   // [4 waves][3][H]
-    if (seed_off) seed += *seed_off;
-    constexpr int RF = LNB_ROWS / 8;                              // rows per half wave
-    const int hl = threadIdx.x & 31, hw = threadIdx.x >> 5, w = threadIdx.x >> 6;
-    const int nchunk8 = H >> 3, nchunk4 = H >> 2;
-    const float inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
-    f32x8 dg[PER], db[PER], dy[PER], gm[PER];
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        dg[t].lo = 0.f; dg[t].hi = 0.f; db[t].lo = 0.f; db[t].hi = 0.f; dy[t].lo = 0.f; dy[t].hi = 0.f;
-        const int c = hl + 32 * t < nchunk8 ? hl + 32 * t : nchunk8 - 1;
-        const f32x4* gp = reinterpret_cast<const f32x4*>(gamma + 8 * c);
-        gm[t].lo = gp[0]; gm[t].hi = gp[1];
-    }
-    const int64_t row0 = (int64_t)blockIdx.x * LNB_ROWS + hw * RF;
-    // 1. every load of these rows goes out first (rows past N are clamped and weighted 0: no branch around a load)
-    f32x8 go[RF][PER], x[RF][PER];
-    float mu[RF], rs[RF], live[RF];
-#pragma unroll
-    for (int r = 0; r < RF; ++r) {
-        const int64_t row = row0 + r < N ? row0 + r : N - 1;
-        live[r] = row0 + r < N ? 1.0f : 0.0f;
-        mu[r] = mean[row]; rs[r] = rstd[row];
-#pragma unroll
-        for (int t = 0; t < PER; ++t) {
-            const int c = hl + 32 * t < nchunk8 ? hl + 32 * t : nchunk8 - 1;
-            const size_t off = (size_t)row * H + 8 * c;
-            go[r][t] = IO<KVQ_BF16>::load8(g_out, off);
-            x[r][t] = IO<KVQ_BF16>::load8(pre, off);
-        }
-    }
-    // 2. the dropout keep bits do not depend on the loads: Philox runs while they are in flight (8 bits per chunk)
-    unsigned keepbits[RF];
-#pragma unroll
-    for (int r = 0; r < RF; ++r) {
-        keepbits[r] = ~0u;
-        if ((g_y || drop_on_out) && p_drop > 0.f) {
-            unsigned kb = 0;
-#pragma unroll
-            for (int t = 0; t < PER; ++t) {
-                const int c = hl + 32 * t;
-                const U4 b0 = drop_bits(seed, site, (unsigned long long)(row0 + r) * nchunk4 + 2 * c);
-                const U4 b1 = drop_bits(seed, site, (unsigned long long)(row0 + r) * nchunk4 + 2 * c + 1);
-                kb |= ((b0.x >= thresh ? 1u : 0u) | (b0.y >= thresh ? 2u : 0u) | (b0.z >= thresh ? 4u : 0u) | (b0.w >= thresh ? 8u : 0u) |
-                       (b1.x >= thresh ? 16u : 0u) | (b1.y >= thresh ? 32u : 0u) | (b1.z >= thresh ? 64u : 0u) | (b1.w >= thresh ? 128u : 0u)) << (8 * t);
-            }
-            keepbits[r] = kb;
-        }
-    }
-    // 3. row statistics, then the outputs
-    float s1[RF], s2[RF];
-#pragma unroll
-    for (int r = 0; r < RF; ++r) {
-        float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-        for (int t = 0; t < PER; ++t) {
-            const float m = (hl + 32 * t < nchunk8) ? live[r] : 0.0f;
-            f32x4 g0 = go[r][t].lo * m, g1 = go[r][t].hi * m;
-            if (drop_on_out) {                       // see drln_bwd_kernel
-                const unsigned kb = keepbits[r] >> (8 * t);
-                g0.x = IO<KVQ_BF16>::round(g0.x * ((kb & 1u) ? inv_keep : 0.f)); g0.y = IO<KVQ_BF16>::round(g0.y * ((kb & 2u) ? inv_keep : 0.f));
-                g0.z = IO<KVQ_BF16>::round(g0.z * ((kb & 4u) ? inv_keep : 0.f)); g0.w = IO<KVQ_BF16>::round(g0.w * ((kb & 8u) ? inv_keep : 0.f));
-                g1.x = IO<KVQ_BF16>::round(g1.x * ((kb & 16u) ? inv_keep : 0.f)); g1.y = IO<KVQ_BF16>::round(g1.y * ((kb & 32u) ? inv_keep : 0.f));
-                g1.z = IO<KVQ_BF16>::round(g1.z * ((kb & 64u) ? inv_keep : 0.f)); g1.w = IO<KVQ_BF16>::round(g1.w * ((kb & 128u) ? inv_keep : 0.f));
-            }
-            const f32x4 xh0 = (x[r][t].lo - mu[r]) * rs[r], xh1 = (x[r][t].hi - mu[r]) * rs[r];
-            const f32x4 t0 = g0 * gm[t].lo, t1 = g1 * gm[t].hi;
-            dg[t].lo += g0 * xh0; dg[t].hi += g1 * xh1;
-            db[t].lo += g0; db[t].hi += g1;
-            a1 += ((t0.x + t0.y) + (t0.z + t0.w)) + ((t1.x + t1.y) + (t1.z + t1.w));
-            a2 += ((t0.x * xh0.x + t0.y * xh0.y) + (t0.z * xh0.z + t0.w * xh0.w)) + ((t1.x * xh1.x + t1.y * xh1.y) + (t1.z * xh1.z + t1.w * xh1.w));
-            go[r][t].lo = t0; go[r][t].hi = t1; x[r][t].lo = xh0; x[r][t].hi = xh1;
-        }
-        s1[r] = a1; s2[r] = a2;
-    }
-#pragma unroll
-    for (int r = 0; r < RF; ++r) {
-        s1[r] = half_wave_sum_f32(s1[r]) / (float)H;
-        s2[r] = half_wave_sum_f32(s2[r]) / (float)H;
-    }
-#pragma unroll
-    for (int r = 0; r < RF; ++r) {
-        if (row0 + r < N) {                          // uniform over the half wave; only stores below
-#pragma unroll
-            for (int t = 0; t < PER; ++t) {
-                const int c = hl + 32 * t;
-                if (c < nchunk8) {
-                    const size_t off = (size_t)(row0 + r) * H + 8 * c;
-                    f32x8 gp;
-                    gp.lo = (go[r][t].lo - s1[r] - x[r][t].lo * s2[r]) * rs[r];
-                    gp.hi = (go[r][t].hi - s1[r] - x[r][t].hi * s2[r]) * rs[r];
-                    if (g_resid) IO<KVQ_BF16>::store8(g_resid, off, gp);
-                    if (g_y) {
-                        if (!drop_on_out) {
-                            const unsigned kb = keepbits[r] >> (8 * t);
-                            gp.lo.x *= (kb & 1u) ? inv_keep : 0.f; gp.lo.y *= (kb & 2u) ? inv_keep : 0.f;
-                            gp.lo.z *= (kb & 4u) ? inv_keep : 0.f; gp.lo.w *= (kb & 8u) ? inv_keep : 0.f;
-                            gp.hi.x *= (kb & 16u) ? inv_keep : 0.f; gp.hi.y *= (kb & 32u) ? inv_keep : 0.f;
-                            gp.hi.z *= (kb & 64u) ? inv_keep : 0.f; gp.hi.w *= (kb & 128u) ? inv_keep : 0.f;
-                        }
-                        IO<KVQ_BF16>::store8(g_y, off, gp);
-                        // what the consumer of g_y reads back is the STORED (bf16-rounded) value
-                        dy[t].lo.x += IO<KVQ_BF16>::round(gp.lo.x); dy[t].lo.y += IO<KVQ_BF16>::round(gp.lo.y);
-                        dy[t].lo.z += IO<KVQ_BF16>::round(gp.lo.z); dy[t].lo.w += IO<KVQ_BF16>::round(gp.lo.w);
-                        dy[t].hi.x += IO<KVQ_BF16>::round(gp.hi.x); dy[t].hi.y += IO<KVQ_BF16>::round(gp.hi.y);
-                        dy[t].hi.z += IO<KVQ_BF16>::round(gp.hi.z); dy[t].hi.w += IO<KVQ_BF16>::round(gp.hi.w);
-                    }
-                }
-            }
-        }
-    }
-    // the two halves of a wave hold the same columns: add them, then the 4 waves through LDS as in drln_bwd_kernel
-    float* l_dy = lds + (size_t)w * 3 * H;
-    float* l_dg = l_dy + H;
-    float* l_db = l_dg + H;
-#pragma unroll
-    for (int t = 0; t < PER; ++t) {
-        f32x8 a = dy[t], b = dg[t], c3 = db[t];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            a.lo[j] += __shfl_xor(a.lo[j], 32, WAVE); a.hi[j] += __shfl_xor(a.hi[j], 32, WAVE);
-            b.lo[j] += __shfl_xor(b.lo[j], 32, WAVE); b.hi[j] += __shfl_xor(b.hi[j], 32, WAVE);
-            c3.lo[j] += __shfl_xor(c3.lo[j], 32, WAVE); c3.hi[j] += __shfl_xor(c3.hi[j], 32, WAVE);
-        }
-        const int c = hl + 32 * t;
-        if ((threadIdx.x & 32) == 0 && c < nchunk8) {
-            f32x4* py = reinterpret_cast<f32x4*>(l_dy + 8 * c); py[0] = a.lo; py[1] = a.hi;
-            f32x4* pg = reinterpret_cast<f32x4*>(l_dg + 8 * c); pg[0] = b.lo; pg[1] = b.hi;
-            f32x4* pb = reinterpret_cast<f32x4*>(l_db + 8 * c); pb[0] = c3.lo; pb[1] = c3.hi;
-        }
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < 3 * H; j += 256) {
-        if (j < H && !want_dbias) continue;
-        float a = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < 4; ++ww) a += lds[(size_t)ww * 3 * H + j];
-        part_dgamma[(size_t)blockIdx.x * 3 * H + j] = a;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // column sums: out[c] = sum_n x[n,c]  (bias gradients; also the second stage of the LN partials).
@@ -2552,166 +2076,6 @@ int kvq_nn_diag_set_buffer(void* buf) {       // diagnostic library only: [workg
     return hipMemcpyToSymbol(HIP_SYMBOL(kvq::g_nn_diag), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
 }
 #endif
-
-static int drln_fwd_impl(const void* y, const void* resid, const float* gamma, const float* beta, int64_t N, int H,
-                         float eps, float p_drop, uint64_t seed, uint32_t site, int io_dtype, void* out, void* pre,
-                         float* mean, float* rstd, unsigned char* out8, float* st8, void* stream);
-
-int kvq_dropout_residual_ln_fwd(const void* y, const void* resid, const float* gamma, const float* beta, int64_t N, int H,
-                                float eps, float p_drop, uint64_t seed, uint32_t site, int io_dtype, void* out, void* pre,
-                                float* mean, float* rstd, void* stream) {
-    return drln_fwd_impl(y, resid, gamma, beta, N, H, eps, p_drop, seed, site, io_dtype, out, pre, mean, rstd, nullptr, nullptr, stream);
-}
-
-int kvq_dropout_residual_ln_fwd_fp8(const void* y, const void* resid, const float* gamma, const float* beta, int64_t N, int H,
-                                    float eps, float p_drop, uint64_t seed, uint32_t site, void* out, void* pre, float* mean, float* rstd,
-                                    void* out_fp8, float* fp8_state, void* stream) {
-    KVQ_REQUIRE(out_fp8 && fp8_state && ((uintptr_t)out_fp8 & 3) == 0, "kvq_dropout_residual_ln_fwd_fp8: null / misaligned fp8 output or state");
-    return drln_fwd_impl(y, resid, gamma, beta, N, H, eps, p_drop, seed, site, KVQ_BF16, out, pre, mean, rstd, (unsigned char*)out_fp8, fp8_state, stream);
-}
-
-static int drln_fwd_impl(const void* y, const void* resid, const float* gamma, const float* beta, int64_t N, int H,
-                         float eps, float p_drop, uint64_t seed, uint32_t site, int io_dtype, void* out, void* pre,
-                         float* mean, float* rstd, unsigned char* out8, float* st8, void* stream) {
-    KVQ_REQUIRE(y && gamma && beta && out && N > 0 && H > 0, "kvq_dropout_residual_ln_fwd: bad argument");
-    KVQ_REQUIRE(H % 4 == 0 && H <= 64 * 4 * LN_MAX_PER_LANE, "kvq_dropout_residual_ln_fwd: H=%d must be a multiple of 4 and <= 4096", H);
-    KVQ_REQUIRE(io_dtype == KVQ_F32 || io_dtype == KVQ_BF16, "unsupported io dtype %d", io_dtype);
-    KVQ_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "p_drop out of range");
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)((N + 3) / 4));
-    const unsigned th = drop_threshold(p_drop);
-#define LAUNCH_LN_FWD(DTV, PERV)                                                                                          \
-    hipLaunchKernelGGL((drln_fwd_kernel<DTV, PERV>), grid, dim3(256), 0, st, y, resid, gamma, beta, N, H, eps, p_drop, th, \
-                       (unsigned long long)seed, g_seed_off, site, out, pre, mean, rstd, out8, st8)
-    if (!resid && H <= 768 && io_dtype == KVQ_BF16) {          // LayerNorm alone (the dense layer's epilogue added the residual)
-        hipLaunchKernelGGL((drln_fwd_kernel<KVQ_BF16, 3, false>), grid, dim3(256), 0, st, y, resid, gamma, beta, N, H, eps, p_drop, th,
-                           (unsigned long long)seed, g_seed_off, site, out, pre, mean, rstd, out8, st8);
-    } else
-    if (H <= 768) { DISPATCH_DT(io_dtype, LAUNCH_LN_FWD(KVQ_F32, 3), LAUNCH_LN_FWD(KVQ_BF16, 3)); }
-    else if (H <= 1024) { DISPATCH_DT(io_dtype, LAUNCH_LN_FWD(KVQ_F32, 4), LAUNCH_LN_FWD(KVQ_BF16, 4)); }
-    else { DISPATCH_DT(io_dtype, LAUNCH_LN_FWD(KVQ_F32, 16), LAUNCH_LN_FWD(KVQ_BF16, 16)); }
-#undef LAUNCH_LN_FWD
-    return check_launch("drln_fwd_kernel");
-}
-
-size_t kvq_ln_bwd_workspace_bytes(int64_t N, int H) {
-    const int64_t blocks = (N + LNB_ROWS - 1) / LNB_ROWS;
-    return (size_t)blocks * H * 3 * sizeof(float);
-}
-
-static int colsum_f32_partials(const float* part, int64_t P, int64_t C, int64_t ldp, void* out, int out_dtype, float scale,
-                               int accumulate, hipStream_t st) {
-    // the final sum of partial rows is the one-item case of the batched reduction: same kernel, same summation order
-    kvq_reduce_item it = {};
-    it.src = part; it.dst = out; it.count = P; it.cols = C; it.ld = ldp; it.scale = scale;
-    it.src_dtype = KVQ_F32; it.dst_dtype = out_dtype; it.accumulate = accumulate;
-    return kvq_reduce_batch(&it, 1, st);
-}
-
-int64_t kvq_ln_bwd_partial_rows(int64_t N) { return (N + LNB_ROWS - 1) / LNB_ROWS; }
-
-static int ln_bwd_partial_impl(const void* g_out, const void* pre, const float* mean, const float* rstd,
-                               const float* gamma, int64_t N, int H, float p_drop, uint64_t seed, uint32_t site,
-                               int io_dtype, void* g_y, void* g_resid, int want_dbias, void* part, size_t part_bytes,
-                               void* stream, int drop_on_out) {
-    KVQ_REQUIRE(g_out && pre && mean && rstd && gamma && N > 0 && H > 0, "kvq_dropout_residual_ln_bwd: bad argument");
-    KVQ_REQUIRE(H % 4 == 0 && H <= 3072, "kvq_dropout_residual_ln_bwd: H=%d unsupported (multiple of 4, <= 3072: 48*H bytes of LDS)", H);
-    KVQ_REQUIRE(io_dtype == KVQ_F32 || io_dtype == KVQ_BF16, "unsupported io dtype %d", io_dtype);
-    const size_t need = kvq_ln_bwd_workspace_bytes(N, H);
-    if (!part || part_bytes < need) return fail(KVQ_E_WORKSPACE, "kvq_dropout_residual_ln_bwd: workspace %zu < %zu", part_bytes, need);
-    KVQ_REQUIRE(!want_dbias || g_y, "kvq_dropout_residual_ln_bwd: the dense-bias partials need g_y");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t blocks = (N + LNB_ROWS - 1) / LNB_ROWS;
-    float* pdg = (float*)part;
-    const size_t lds = (size_t)4 * 3 * H * sizeof(float);
-    const unsigned th = drop_threshold(p_drop);
-    if (io_dtype == KVQ_BF16 && H % 8 == 0 && H <= 1024 && H >= 64 && LNB_ROWS % 8 == 0 &&
-        ((((uintptr_t)g_out | (uintptr_t)pre | (uintptr_t)g_y | (uintptr_t)g_resid | (uintptr_t)gamma) & 15) == 0)) {
-#define LAUNCH_LN_BWD16(PERV)                                                                                              \
-    hipLaunchKernelGGL((drln_bwd16_kernel<PERV>), dim3((unsigned)blocks), dim3(256), lds, st, g_out, pre, mean, rstd, gamma,  \
-                       N, H, p_drop, th, (unsigned long long)seed, g_seed_off, site, g_y, g_resid, pdg, want_dbias ? 1 : 0, drop_on_out)
-        if (H <= 256) LAUNCH_LN_BWD16(1);
-        else if (H <= 512) LAUNCH_LN_BWD16(2);
-        else if (H <= 768) LAUNCH_LN_BWD16(3);
-        else LAUNCH_LN_BWD16(4);
-#undef LAUNCH_LN_BWD16
-        return check_launch("drln_bwd16_kernel");
-    }
-#define LAUNCH_LN_BWD(DTV, PERV)                                                                                             \
-    hipLaunchKernelGGL((drln_bwd_kernel<DTV, PERV>), dim3((unsigned)blocks), dim3(256), lds, st, g_out, pre, mean, rstd, gamma, \
-                       N, H, p_drop, th, (unsigned long long)seed, g_seed_off, site, g_y, g_resid, pdg, want_dbias ? 1 : 0, drop_on_out)
-    if (H <= 768) { DISPATCH_DT(io_dtype, LAUNCH_LN_BWD(KVQ_F32, 3), LAUNCH_LN_BWD(KVQ_BF16, 3)); }
-    else if (H <= 1024) { DISPATCH_DT(io_dtype, LAUNCH_LN_BWD(KVQ_F32, 4), LAUNCH_LN_BWD(KVQ_BF16, 4)); }
-    else { DISPATCH_DT(io_dtype, LAUNCH_LN_BWD(KVQ_F32, 16), LAUNCH_LN_BWD(KVQ_BF16, 16)); }
-#undef LAUNCH_LN_BWD
-    return check_launch("drln_bwd_kernel");
-}
-
-int kvq_dropout_residual_ln_bwd_partial(const void* g_out, const void* pre, const float* mean, const float* rstd,
-                                        const float* gamma, int64_t N, int H, float p_drop, uint64_t seed, uint32_t site,
-                                        int io_dtype, void* g_y, void* g_resid, int want_dbias, void* part, size_t part_bytes,
-                                        void* stream) {
-    return ln_bwd_partial_impl(g_out, pre, mean, rstd, gamma, N, H, p_drop, seed, site, io_dtype, g_y, g_resid, want_dbias, part,
-                               part_bytes, stream, 0);
-}
-
-int kvq_ln_dropout_bwd_partial(const void* g_out, const void* pre, const float* mean, const float* rstd, const float* gamma,
-                               int64_t N, int H, float p_drop, uint64_t seed, uint32_t site, int io_dtype, void* g_y,
-                               void* part, size_t part_bytes, void* stream) {
-    return ln_bwd_partial_impl(g_out, pre, mean, rstd, gamma, N, H, p_drop, seed, site, io_dtype, g_y, nullptr, 0, part, part_bytes,
-                               stream, 1);
-}
-
-int kvq_embed_ln_fwd(const int64_t* ids, const void* word, const void* pos, const void* type_row, const float* gamma,
-                     const float* beta, int64_t N, int S, int H, int64_t V, float eps, float p_drop, uint64_t seed, uint32_t site,
-                     int io_dtype, void* out, void* pre, float* mean, float* rstd, void* stream) {
-    KVQ_REQUIRE(ids && word && pos && type_row && gamma && beta && out && N > 0 && S > 0 && H > 0 && V > 0, "kvq_embed_ln_fwd: bad argument");
-    KVQ_REQUIRE(H % 4 == 0 && H <= 64 * 4 * LN_MAX_PER_LANE, "kvq_embed_ln_fwd: H=%d must be a multiple of 4 and <= 4096", H);
-    KVQ_REQUIRE(io_dtype == KVQ_F32 || io_dtype == KVQ_BF16, "unsupported io dtype %d", io_dtype);
-    KVQ_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "p_drop out of range");
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)((N + 3) / 4));
-    const unsigned th = drop_threshold(p_drop);
-#define LAUNCH_EMB(DTV, PERV)                                                                                                  \
-    hipLaunchKernelGGL((embed_ln_fwd_kernel<DTV, PERV>), grid, dim3(256), 0, st, ids, word, pos, type_row, gamma, beta, N, S, H, V, \
-                       eps, p_drop, th, (unsigned long long)seed, g_seed_off, site, out, pre, mean, rstd)
-    if (H <= 768) { DISPATCH_DT(io_dtype, LAUNCH_EMB(KVQ_F32, 3), LAUNCH_EMB(KVQ_BF16, 3)); }
-    else if (H <= 1024) { DISPATCH_DT(io_dtype, LAUNCH_EMB(KVQ_F32, 4), LAUNCH_EMB(KVQ_BF16, 4)); }
-    else { DISPATCH_DT(io_dtype, LAUNCH_EMB(KVQ_F32, 16), LAUNCH_EMB(KVQ_BF16, 16)); }
-#undef LAUNCH_EMB
-    return check_launch("embed_ln_fwd_kernel");
-}
-
-int kvq_dropout_residual_ln_bwd(const void* g_out, const void* pre, const float* mean, const float* rstd, const float* gamma,
-                                int64_t N, int H, float p_drop, uint64_t seed, uint32_t site, int io_dtype, void* g_y,
-                                void* g_resid, void* g_gamma, void* g_beta, void* g_bias_prev, int param_grad_dtype, int accumulate,
-                                void* ws, size_t ws_bytes, void* stream) {
-    int rc = kvq_dropout_residual_ln_bwd_partial(g_out, pre, mean, rstd, gamma, N, H, p_drop, seed, site, io_dtype, g_y, g_resid,
-                                                 g_bias_prev ? 1 : 0, ws, ws_bytes, stream);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t blocks = (N + LNB_ROWS - 1) / LNB_ROWS;
-    float* pdg = (float*)ws;
-    const size_t esz = param_grad_dtype == KVQ_F32 ? 4 : 2;
-    const int64_t H3 = 3 * (int64_t)H;
-    const bool gb_adj = g_gamma && g_beta && (char*)g_beta == (char*)g_gamma + (size_t)H * esz;
-    const bool all_adj = gb_adj && g_bias_prev && (char*)g_gamma == (char*)g_bias_prev + (size_t)H * esz;
-    if (all_adj) {
-        // [dense bias | LN weight | LN bias] are adjacent in the engine's flat layout: ONE pass writes all three
-        rc = colsum_f32_partials(pdg, blocks, H3, H3, g_bias_prev, param_grad_dtype, 1.0f, accumulate, st);
-        if (rc) return rc;
-    } else {
-        if (g_bias_prev) { rc = colsum_f32_partials(pdg, blocks, H, H3, g_bias_prev, param_grad_dtype, 1.0f, accumulate, st); if (rc) return rc; }
-        if (gb_adj) {
-            rc = colsum_f32_partials(pdg + H, blocks, 2 * (int64_t)H, H3, g_gamma, param_grad_dtype, 1.0f, accumulate, st);
-            if (rc) return rc;
-        } else {
-            if (g_gamma) { rc = colsum_f32_partials(pdg + H, blocks, H, H3, g_gamma, param_grad_dtype, 1.0f, accumulate, st); if (rc) return rc; }
-            if (g_beta) { rc = colsum_f32_partials(pdg + 2 * H, blocks, H, H3, g_beta, param_grad_dtype, 1.0f, accumulate, st); if (rc) return rc; }
-        }
-    }
-    return KVQ_OK;
-}
 
 size_t kvq_colsum_workspace_bytes(int64_t N, int64_t C) { return (size_t)((N + CS_ROWS - 1) / CS_ROWS) * C * sizeof(float); }
 

@@ -1,4 +1,4 @@
-"""Tensor-level wrappers of the fused block kernels in libkvq.so (csrc/kvq_nn.hip).  Plain functions, no autograd:
+"""Tensor-level wrappers of the fused block kernels in libkvq.so (csrc/kvq_nn.hip, csrc/kvq_ln.hip).  Plain functions, no autograd:
 the training engine (kvq/engine.py) calls forward and backward kernels explicitly.  All work goes to the current stream."""
 from __future__ import annotations
 

@@ -1,4 +1,4 @@
-"""bf16 LayerNorm with dropout on (csrc/kvq_nn.hip: drln_fwd_kernel, drln_bwd16_kernel -- the backward the step runs --, and the
+"""bf16 LayerNorm with dropout on (csrc/kvq_ln.hip: drln_fwd_kernel, drln_bwd16_kernel -- the backward the step runs --, and the
 generic drln_bwd_kernel<KVQ_BF16>) against an f64 reference under the mask the kernel really drew, judged per row with the
 envelope of tests/_attn_ref.py, every output inside a frame that must stay untouched bit for bit.
 

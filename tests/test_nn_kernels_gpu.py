@@ -1,4 +1,4 @@
-"""GPU numerics of the fused block kernels (csrc/kvq_nn.hip) against plain PyTorch f32 references of the same ops
+"""GPU numerics of the fused block kernels (csrc/kvq_nn.hip, csrc/kvq_ln.hip) against plain PyTorch f32 references of the same ops
 (the ops HuggingFace's BertLayer runs: modeling_bert.py:111-352) and torch.optim.Adam."""
 import math
 
@@ -59,7 +59,7 @@ def test_ln_fwd_bwd_no_dropout(ops, N, H, dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("H,p", [(768, 0.1), (128, 0.0), (1024, 0.25)])
+@pytest.mark.parametrize("H,p", [(768, 0.1), (128, 0.0), (1024, 0.25), (2048, 0.1)])
 def test_embedding_block_kernels_equal_the_separate_kernels(ops, dtype, H, p):
     """BertEmbeddings (modeling_bert.py:53-110): kvq_embed_ln_fwd == gather + (pos + type) + kvq_dropout_residual_ln_fwd +
     kvq_dropout bit for bit, and kvq_ln_dropout_bwd_partial == kvq_dropout on the gradient + the LayerNorm backward; the
