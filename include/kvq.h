@@ -810,6 +810,58 @@ int kvq_gumbel_backward(const void* logits, const float* y_soft, const void* g_y
                         float kld_scale, int io_dtype, void* g_logits, void* stream);
 
 
+/* ---- free-running generation: one decoder token per sentence and launch, over a key/value cache (csrc/kvq_generate.hip) --------
+ * What the teacher-forced decoder call (models/bagon/Bagon.py:46-53, models/shelgon3/Shelgon.py:71) cannot answer: the sentence a
+ * latent produces when the decoder sees only what it has written itself.  DESIGN.md section 5i.
+ *
+ * Generation state, on the device (the pattern of the accumulation state): 32 bytes, 8-byte aligned,
+ *     struct { int32 t, P, Lmax, eos_id, pad_id; uint32 seed_lo, seed_hi; float inv_tau; }
+ *   t = the position being decoded (the token at column t of `ids` is the step's input), P = prompt length (columns 0 .. P-1 of
+ *   `ids` are given), Lmax = columns of `ids`, eos_id < 0 = no end token; seed = the 64-bit Philox key of the sampling draws,
+ *   inv_tau = 1 / temperature, 0 = greedy.  Beside it ids [B, Lmax] int64, finished [B] int32,
+ *   lengths [B] int32.  EVERY kernel below reads t from the state, never from a launch argument: one captured step serves every
+ *   position.  Kernels only, no floating-point atomics (no atomics at all), the same inputs give the same bits; f32 and bf16 io.
+ *   A state whose t lies outside what the buffers hold (t >= Lmax, t >= pos_rows, t >= Smax) makes the kernels store nothing.
+ *
+ * kvq_gen_embed   BertEmbeddings (modeling_bert.py:53-110) of one token per sentence at evaluation:
+ *                     out[b, :] = LayerNorm(word[ids[b, t]] + (pos[t] + type_row))            out [B, H] io dtype
+ *                 with the arithmetic, roundings and summation order of kvq_embed_ln_fwd (p_drop = 0): the bits of its row for the
+ *                 same token at the same position.  pos has pos_rows rows.  H %% 4 == 0, H <= 4096.
+ * kvq_gen_attn    BertSelfAttention / cross-attention core (:111-204) for ONE query row per (sentence, head), head dim 64:
+ *                     out[b, h*64 ..] = softmax(q[b, h] . K[b, :n, h]^T * 1/8) . V[b, :n, h]
+ *                 q [B, ldq], out [B, ldo]; kv: keys at column h*64, values at column nh*64 + h*64 of row j of sentence b, at
+ *                 kv + b * kv_sentence_stride + j * ld_kv (elements).
+ *                   append != 0 (self-attention): k_new / v_new [B, ld_new] are this step's rows (column slices of the fused q|k|v
+ *                     projection); the kernel stores them to row t of the cache kv [B, Smax, 2 nh 64] and attends over rows 0 .. t
+ *                     (n = t + 1, n_keys is ignored).  A workgroup owns one (sentence, head) and touches only that head's columns.
+ *                   append == 0 (cross-attention): n = n_keys, 1 .. 128; kv is a layer's column slice of the projected latent
+ *                     (ld_kv = the row stride of that buffer); k_new, v_new are ignored.  No mask.
+ *                 Scores and probabilities f32, the output rounded once to the io dtype.  16-byte accesses: every pointer 16-byte
+ *                 aligned, every stride a multiple of 16 bytes.  Smax <= 128.
+ * kvq_gen_select  the next token of every sentence from logits [B, ld] io dtype (columns >= V never win), one workgroup a sentence:
+ *                     choice = first arg-max over v < V of (logit_v * inv_tau + g_v); a NaN never wins (a row of NaNs chooses 0)
+ *                   inv_tau and seed are read from the state, as t is: the same launch serves every temperature and seed.
+ *                   state.inv_tau == 0: g = 0 and inv_tau = 1 (greedy).  Otherwise g_v = -log(-log u), u from
+ *                     philox4x32(c0 = v / 4, c1 = b, c2 = t, c3 = 0x47454e53; key = seed) word v %% 4, u = ((bits >> 9) + 0.5) 2^-23,
+ *                     which is exact in f32 and inside [2^-24, 1 - 2^-24], so g is finite for every bit pattern: the Gumbel-max
+ *                     trick, a draw from softmax(logits * inv_tau) (on a grid of 2^23 uniforms).
+ *                     kvq_gen_gumbel_debug (test hook): out[i] = g of bits[i] as the kernel forms it.
+ *                   then, when t + 1 < Lmax:  t + 1 < P: ids[b, t+1] is kept (prompt);  else finished[b]: ids[b, t+1] = pad_id;
+ *                     else ids[b, t+1] = choice and, if choice == eos_id, finished[b] = 1 and lengths[b] = t + 2.
+ *                   step_logits (may be NULL) [B, Lmax, V] f32: row (b, t) receives the logits of columns < V.
+ *                 ld %% 8 == 0, 16-byte aligned logits.
+ * kvq_gen_advance one thread: t += 1.  A launch of its own, so that no kernel of a step races with the increment. */
+int kvq_gen_embed(const void* state, const int64_t* ids, const void* word, const void* pos, const void* type_row, const float* gamma,
+                  const float* beta, int B, int H, int64_t V, int pos_rows, float eps, int io_dtype, void* out, void* stream);
+int kvq_gen_attn(const void* state, const void* q, int64_t ldq, const void* k_new, const void* v_new, int64_t ld_new, void* kv,
+                 int64_t ld_kv, int64_t kv_sentence_stride, int B, int nh, int append, int n_keys, int Smax, int io_dtype, void* out,
+                 int64_t ldo, void* stream);
+int kvq_gen_select(const void* state, const void* logits, int64_t ld, int V, int B, int io_dtype, int64_t* ids, int32_t* finished,
+                   int32_t* lengths, float* step_logits, void* stream);
+int kvq_gen_gumbel_debug(const uint32_t* bits, int64_t n, float* out, void* stream);
+int kvq_gen_advance(void* state, void* stream);
+
+
 #ifdef __cplusplus
 }
 #endif

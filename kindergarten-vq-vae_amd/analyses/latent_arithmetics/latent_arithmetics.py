@@ -63,6 +63,7 @@ VQ_E_DIM = 768
 VQ_BETA = 0.1
 CKPT_PATH = None                     # "<RUN_DIR>/bagon_ckpt_loss_recon_val_best.pth" (:55); None = fresh weights
 RESULTS_DIR = None                   # default: <RUN_DIR>
+FREE_RUNNING = False                 # True (or --free-running on the command line): the plain and the edited latent are GENERATED from each sentence's first token (model.generate_from_latents) instead of decoded against the sentence's own ids; for a model trained with DECODER_NEXT_TOKEN
 
 for _k in [k for k in list(globals()) if k.isupper()]:
     _v = os.environ.get("KVQ_" + _k)
@@ -94,7 +95,8 @@ def _tokenize(tokenizer, sentences, device, seq_len, add_special_tokens):
     return t.input_ids.to(device, non_blocking=True), t.attention_mask.to(device, non_blocking=True)
 
 
-def latent_arithmetics(model, tokenizer, s_neg, s_aff, s_edit, device, seq_len, batch_size, add_special_tokens=False, alpha=1.0):
+def latent_arithmetics(model, tokenizer, s_neg, s_aff, s_edit, device, seq_len, batch_size, add_special_tokens=False, alpha=1.0,
+                       free_running=False):
     """-> (LatentCensus over group 0 = s_aff, group 1 = s_neg; rows of original / reconstructed / edited sentences of s_edit)"""
     H = model.encoder.config.hidden_size
     quantize = hasattr(model, "vector_quantizer")
@@ -107,8 +109,13 @@ def latent_arithmetics(model, tokenizer, s_neg, s_aff, s_edit, device, seq_len, 
     for batch in _batches(s_edit, batch_size):                                               # :94-139
         ids, mask = _tokenize(tokenizer, batch, device, seq_len, add_special_tokens)
         z = model.encode_latents(ids, mask, quantize=False)["z"]
-        plain = model.decode_latents(z, ids, mask, quantize=quantize)["recon_ids"]
-        edited = model.decode_latents(census.shift(z, 1, 0, alpha=alpha), ids, mask, quantize=quantize)["recon_ids"]
+        if free_running:                        # what the latent says by itself: the decoder sees the first token and its own output
+            start = ids[:, :1].contiguous()
+            plain = model.generate_from_latents(z, seq_len, start, quantize=quantize)["ids"]
+            edited = model.generate_from_latents(census.shift(z, 1, 0, alpha=alpha), seq_len, start, quantize=quantize)["ids"]
+        else:
+            plain = model.decode_latents(z, ids, mask, quantize=quantize)["recon_ids"]
+            edited = model.decode_latents(census.shift(z, 1, 0, alpha=alpha), ids, mask, quantize=quantize)["recon_ids"]
         for s, r, e in zip(batch, tokenizer.batch_decode(plain.cpu()), tokenizer.batch_decode(edited.cpu())):
             rows.append({"input_sentence": s, "recon_sentence": r, "edited_sentence": e})
     return census, rows
@@ -149,7 +156,7 @@ def main():
     torch.set_grad_enabled(False)                                                            # :45
     tokenizer = load_tokenizer(TOKENIZER_NAME)
     census, rows = latent_arithmetics(model, tokenizer, s_neg, s_aff, s_edit, device, TOKENIZED_SENTENCE_MAX_LENGTH, BATCH_SIZE,
-                                      TOKENIZER_ADD_SPECIAL_TOKENS, ALPHA)
+                                      TOKENIZER_ADD_SPECIAL_TOKENS, ALPHA, free_running=bool(FREE_RUNNING) or "--free-running" in sys.argv[1:])
     results_dir = RESULTS_DIR or run_dir
     os.makedirs(results_dir, exist_ok=True)
     written = write_table(pd.DataFrame(rows), f"{results_dir}/latent_arithmetics.feather")

@@ -58,6 +58,7 @@ VQ_BETA = 0.1
 VQ_N_FACTORS = 1
 CKPT_PATH = None                     # "<RUN_DIR>/Shelgon_ckpt_loss_recon_val_best.pth" (:55); None = fresh weights
 RESULTS_DIR = None                   # default: <RUN_DIR>
+FREE_RUNNING = False                 # True (or --free-running on the command line): the K variants are GENERATED from the sentence's first token (model.traverse_codes(free_running=True)) instead of decoded against the sentence's own ids; for a model trained with DECODER_NEXT_TOKEN
 
 for _k in [k for k in list(globals()) if k.isupper()]:
     _v = os.environ.get("KVQ_" + _k)
@@ -68,15 +69,15 @@ for _k in [k for k in list(globals()) if k.isupper()]:
             globals()[_k] = _v
 
 
-def code_traversal(model, tokenizer, sentences, device, seq_len, positions=None, factor=0, add_special_tokens=False):
-    """Rows of the result table for every (sentence, position, code)."""
+def code_traversal(model, tokenizer, sentences, device, seq_len, positions=None, factor=0, add_special_tokens=False, free_running=False):
+    """Rows of the result table for every (sentence, position, code).  free_running: the variants are generated, not teacher-forced."""
     t = tokenizer(list(sentences), return_tensors="pt", padding="max_length", max_length=seq_len, add_special_tokens=add_special_tokens)
     ids, mask = t.input_ids.to(device), t.attention_mask.to(device)                          # :98-108
     lengths = t.attention_mask.sum(1).tolist()
     rows = []
     for b, sentence in enumerate(sentences):
         for pos in (positions if positions is not None else range(int(lengths[b]))):
-            out = model.traverse_codes(ids, mask, b, int(pos), factor=factor)                 # :139-150
+            out = model.traverse_codes(ids, mask, b, int(pos), factor=factor, free_running=free_running)      # :139-150
             decoded = tokenizer.batch_decode(out["recon_ids"].cpu())                         # :158-160
             n_changed = out["changed"].sum(1).tolist()
             for k, (r, c) in enumerate(zip(decoded, n_changed)):
@@ -116,7 +117,7 @@ def main():
     torch.set_grad_enabled(False)                                                            # :42
     tokenizer = load_tokenizer(TOKENIZER_NAME)
     rows = code_traversal(model, tokenizer, all_gen_fact, device, TOKENIZED_SENTENCE_MAX_LENGTH, POSITIONS, FACTOR_INDEX,
-                          TOKENIZER_ADD_SPECIAL_TOKENS)
+                          TOKENIZER_ADD_SPECIAL_TOKENS, free_running=bool(FREE_RUNNING) or "--free-running" in sys.argv[1:])
     results_dir = RESULTS_DIR or run_dir
     os.makedirs(results_dir, exist_ok=True)
     written = write_table(pd.DataFrame(rows), f"{results_dir}/code_traversal.feather")

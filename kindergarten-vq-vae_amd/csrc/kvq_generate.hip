@@ -1,0 +1,420 @@
+// kvq_generate.hip -- free-running generation: one decoder token per sentence and launch, over a key/value cache (gfx950).
+//
+// TrainEngine.generate runs the decoder one position at a time: [B, H] rows through the GEMMs the training step uses, and the four
+// kernels of this file for what is not a GEMM or a LayerNorm:
+//     kvq_gen_embed     BertEmbeddings of the token at column t of `ids` (the bits of kvq_embed_ln_fwd's row for it)
+//     kvq_gen_attn      one query row per (sentence, head) against the cache (self-attention: this step's k | v rows are appended
+//                       first) or against the projected latent (cross-attention)
+//     kvq_gen_select    the next token: arg-max of logit / tau + Gumbel noise (none when greedy), prompt / end-token bookkeeping
+//     kvq_gen_advance   one thread: t += 1
+// Every kernel reads the position t from the 32-byte generation state on the device (include/kvq.h), so one captured chain of
+// launches serves every position.  No atomics, fixed summation orders: the same inputs give the same bits.
+//
+// kvq_gen_attn is a read of K and V, at most 128 rows of 64 elements per (sentence, head): 16 bytes per lane straight to
+// registers (8 lanes span a bf16 row, 16 an f32 row; a wave takes 8 resp. 4 keys per instruction, four instructions in flight),
+// no LDS staging of the operands and no MFMA -- a single query row would fill one row of a 32 x 32 tile.  The scores pass through
+// 512 bytes of LDS between the three phases (scores, softmax, P.V).
+#include <math.h>
+
+#include "kvq_common.h"
+#include <type_traits>
+
+namespace kvq {
+
+struct GenState {
+    int32_t t, P, Lmax, eos_id, pad_id;
+    uint32_t seed_lo, seed_hi;      // the Philox key of the sampling draws
+    float inv_tau;                  // 1 / temperature; 0 = greedy (no noise, the logits as they are)
+};
+static_assert(sizeof(GenState) == 32, "the generation state is 32 bytes (include/kvq.h)");
+
+constexpr int GEN_MAX_KEYS = 128;
+constexpr int GEN_LN_MAX_PER_LANE = 16;   // H <= 4096, as csrc/kvq_ln.hip
+
+__device__ __forceinline__ float gen_wave_max(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, WAVE));
+    return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// embedding: embed_ln_fwd_kernel of csrc/kvq_ln.hip for the rows (b, t), restated operation by operation (p_drop = 0): one wave
+// per row, lane `lane` holds the chunks lane + 64 u of 4 elements, the sums in that kernel's order
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float gen_quadsum(f32x4 v) { return (v.x + v.y) + (v.z + v.w); }
+__device__ __forceinline__ float gen_dot4(f32x4 a, f32x4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
+
+template <int DT, int PER>
+__global__ __launch_bounds__(256) void gen_embed_kernel(const GenState* __restrict__ st, const int64_t* __restrict__ ids,
+                                                         const void* __restrict__ word, const void* __restrict__ pos,
+                                                         const void* __restrict__ type_row, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, int B, int H, int64_t V, int pos_rows,
+                                                         float eps, void* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= B) return;
+    const int t = st->t, Lmax = st->Lmax;
+    if (t < 0 || t >= Lmax || t >= pos_rows) return;          // (uniform) a state outside the buffers: nothing is read or stored
+    const int nchunk = H >> 2;
+    int64_t id = ids[(int64_t)row * Lmax + t];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    f32x4 v[PER];
+    float sum = 0.f;
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int c = lane + WAVE * u;
+        f32x4 a = {0.f, 0.f, 0.f, 0.f};
+        if (c < nchunk) {
+            f32x4 pt = IO<DT>::load4(pos, (size_t)t * H + 4 * c) + IO<DT>::load4(type_row, 4 * c);
+            pt.x = IO<DT>::round(pt.x); pt.y = IO<DT>::round(pt.y); pt.z = IO<DT>::round(pt.z); pt.w = IO<DT>::round(pt.w);
+            a = IO<DT>::load4(word, (size_t)id * H + 4 * c) + pt;
+            a.x = IO<DT>::round(a.x); a.y = IO<DT>::round(a.y); a.z = IO<DT>::round(a.z); a.w = IO<DT>::round(a.w);
+            sum += gen_quadsum(a);
+        }
+        v[u] = a;
+    }
+    const float mean = wave_sum_f32(sum) / (float)H;
+    float sq = 0.f;
+#pragma unroll
+    for (int u = 0; u < PER; ++u)
+        if (lane + WAVE * u < nchunk) {
+            const f32x4 d = v[u] - mean;
+            sq += gen_dot4(d, d);
+        }
+    const float var = wave_sum_f32(sq) / (float)H;
+    const float rstd = rsqrtf(var + eps);
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int c = lane + WAVE * u;
+        if (c < nchunk) {
+            const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 4 * c);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(beta + 4 * c);
+            const f32x4 o = (v[u] - mean) * rstd * g + b;
+            IO<DT>::store4(out, (size_t)row * H + 4 * c, o);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// attention of one query row.  One wave per (sentence, head).  EPL elements (16 bytes) per lane, LPR lanes per 64-element row,
+// KPI rows per wave instruction, GEN_UNROLL instructions in flight.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int GEN_UNROLL = 4;
+
+template <int DT>
+struct Chunk;
+template <>
+struct Chunk<KVQ_BF16> {
+    static constexpr int EPL = 8;
+    typedef uint4 raw;
+    __device__ static __forceinline__ void unpack(const raw& r, float (&f)[8]) {
+        f[0] = __uint_as_float(r.x << 16); f[1] = __uint_as_float(r.x & 0xffff0000u);
+        f[2] = __uint_as_float(r.y << 16); f[3] = __uint_as_float(r.y & 0xffff0000u);
+        f[4] = __uint_as_float(r.z << 16); f[5] = __uint_as_float(r.z & 0xffff0000u);
+        f[6] = __uint_as_float(r.w << 16); f[7] = __uint_as_float(r.w & 0xffff0000u);
+    }
+    __device__ static __forceinline__ raw pack(const float (&f)[8]) {
+        raw r;
+        r.x = (unsigned)f32_to_bf16(f[0]) | ((unsigned)f32_to_bf16(f[1]) << 16);
+        r.y = (unsigned)f32_to_bf16(f[2]) | ((unsigned)f32_to_bf16(f[3]) << 16);
+        r.z = (unsigned)f32_to_bf16(f[4]) | ((unsigned)f32_to_bf16(f[5]) << 16);
+        r.w = (unsigned)f32_to_bf16(f[6]) | ((unsigned)f32_to_bf16(f[7]) << 16);
+        return r;
+    }
+};
+template <>
+struct Chunk<KVQ_F32> {
+    static constexpr int EPL = 4;
+    typedef f32x4 raw;
+    __device__ static __forceinline__ void unpack(const raw& r, float (&f)[4]) { f[0] = r.x; f[1] = r.y; f[2] = r.z; f[3] = r.w; }
+    __device__ static __forceinline__ raw pack(const float (&f)[4]) {
+        raw r = {f[0], f[1], f[2], f[3]};
+        return r;
+    }
+};
+
+template <int DT>
+__global__ __launch_bounds__(64) void gen_attn_kernel(const GenState* __restrict__ st, const void* __restrict__ q, int64_t ldq,
+                                                       const void* __restrict__ k_new, const void* __restrict__ v_new, int64_t ld_new,
+                                                       void* kv, int64_t ld_kv, int64_t kv_sentence_stride, int nh, int append,
+                                                       int n_keys, int Smax, void* __restrict__ out, int64_t ldo) {
+    typedef typename IO<DT>::elem elem;
+    typedef Chunk<DT> CH;
+    typedef typename CH::raw raw;
+    constexpr int EPL = CH::EPL, LPR = 64 / EPL, KPI = WAVE / LPR;
+    __shared__ float sc[GEN_MAX_KEYS];
+
+    const int b = blockIdx.x / nh, h = blockIdx.x - b * nh;
+    const int lane = threadIdx.x, sub = lane % LPR, grp = lane / LPR;
+    const int t = st->t;
+    if (append && (t < 0 || t >= Smax)) return;               // (uniform) no row t in the cache: nothing is read or stored
+    const int n = append ? t + 1 : n_keys;                    // 1 .. 128
+    const int col = h * 64 + sub * EPL;
+
+    const elem* kbase = reinterpret_cast<const elem*>(kv) + (size_t)b * kv_sentence_stride + col;
+    const elem* vbase = kbase + (size_t)nh * 64;
+    const elem* knew = append ? reinterpret_cast<const elem*>(k_new) + (size_t)b * ld_new + col : kbase;
+    const elem* vnew = append ? reinterpret_cast<const elem*>(v_new) + (size_t)b * ld_new + col : vbase;
+    const int fresh = append ? t : -1;                        // the key whose row comes from this step's projection, not from the cache
+
+    float qf[EPL];
+    CH::unpack(*reinterpret_cast<const raw*>(reinterpret_cast<const elem*>(q) + (size_t)b * ldq + col), qf);
+
+    if (append && grp < 2) {                                  // this step's k (group 0) and v (group 1) rows go to row t of the cache
+        const raw r = *reinterpret_cast<const raw*>(grp == 0 ? knew : vnew);
+        elem* dst = reinterpret_cast<elem*>(kv) + (size_t)b * kv_sentence_stride + (size_t)t * ld_kv + col + (grp == 0 ? 0 : nh * 64);
+        *reinterpret_cast<raw*>(dst) = r;
+    }
+
+    // ---- scores: s_j = (q . k_j) / 8 ----
+    for (int j0 = 0; j0 < n; j0 += KPI * GEN_UNROLL) {
+        raw r[GEN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GEN_UNROLL; ++u) {
+            const int j = j0 + u * KPI + grp;
+            const int jc = j < n ? j : n - 1;                 // (rows past the last key: a valid row, the score is not stored)
+            r[u] = *reinterpret_cast<const raw*>(jc == fresh ? knew : kbase + (size_t)jc * ld_kv);
+        }
+#pragma unroll
+        for (int u = 0; u < GEN_UNROLL; ++u) {
+            const int j = j0 + u * KPI + grp;
+            float kf[EPL];
+            CH::unpack(r[u], kf);
+            float d = 0.f;
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) d += qf[e] * kf[e];
+#pragma unroll
+            for (int m = LPR / 2; m >= 1; m >>= 1) d += __shfl_xor(d, m, WAVE);
+            if (sub == 0 && j < n) sc[j] = d * 0.125f;
+        }
+    }
+    __syncthreads();
+
+    // ---- softmax over the n scores, f32; the probabilities stay unnormalised until the output ----
+    const float s0 = lane < n ? sc[lane] : -INFINITY, s1 = lane + 64 < n ? sc[lane + 64] : -INFINITY;
+    const float mx = gen_wave_max(fmaxf(s0, s1));
+    const float p0 = lane < n ? __expf(s0 - mx) : 0.f, p1 = lane + 64 < n ? __expf(s1 - mx) : 0.f;
+    const float inv = 1.0f / wave_sum_f32(p0 + p1);
+    __syncthreads();
+    if (lane < n) sc[lane] = p0;
+    if (lane + 64 < n) sc[lane + 64] = p1;
+    __syncthreads();
+
+    // ---- out = (sum_j p_j v_j) / sum_j p_j : each lane group adds its keys in ascending order, then the groups are added ----
+    float acc[EPL];
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
+    for (int j0 = 0; j0 < n; j0 += KPI * GEN_UNROLL) {
+        raw r[GEN_UNROLL];
+        float p[GEN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GEN_UNROLL; ++u) {
+            const int j = j0 + u * KPI + grp;
+            const int jc = j < n ? j : n - 1;
+            r[u] = *reinterpret_cast<const raw*>(jc == fresh ? vnew : vbase + (size_t)jc * ld_kv);
+            p[u] = j < n ? sc[jc] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < GEN_UNROLL; ++u) {
+            float vf[EPL];
+            CH::unpack(r[u], vf);
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) acc[e] += p[u] * vf[e];
+        }
+    }
+#pragma unroll
+    for (int m = LPR; m < WAVE; m <<= 1)
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) acc[e] += __shfl_xor(acc[e], m, WAVE);
+    if (grp == 0) {
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) acc[e] *= inv;
+        *reinterpret_cast<raw*>(reinterpret_cast<elem*>(out) + (size_t)b * ldo + col) = CH::pack(acc);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// next token: one workgroup of 256 threads per sentence
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int SEL_THREADS = 256;
+
+// Gumbel(0, 1) from 32 random bits, FINITE for every bit pattern: u = (k + 1/2) 2^-23 with the 23-bit k = b >> 9 is exact in f32
+// (k + 1/2 needs 24 significant bits) and lies in [2^-24, 1 - 2^-24]; logf (not the fast form, whose absolute error near 1 could
+// round -log u to 0) gives -log u in [5.96e-8, 16.7], so g lies in [-2.82, 16.7].  (With 24 bits, (k + 1/2) rounds to 2^24 for
+// k = 2^24 - 1: u = 1, g = +inf, and that column would win whatever its logit -- once in 550 tokens of a 30522-word vocabulary.)
+__device__ __forceinline__ float gen_gumbel_from_bits(unsigned b) {
+    const float u = ((float)(b >> 9) + 0.5f) * (1.0f / 8388608.0f);
+    return -logf(-logf(u));
+}
+// strictly larger wins, equal -> lower index; a NaN compares false both ways and never wins
+__device__ __forceinline__ bool sel_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+template <int DT>
+__global__ __launch_bounds__(SEL_THREADS) void gen_select_kernel(const GenState* __restrict__ st, const void* __restrict__ logits,
+                                                                  int64_t ld, int V, int64_t* __restrict__ ids, int32_t* __restrict__ finished,
+                                                                  int32_t* __restrict__ lengths, float* __restrict__ step_logits) {
+    __shared__ float wv[SEL_THREADS / WAVE];
+    __shared__ int wi[SEL_THREADS / WAVE];
+    const int b = blockIdx.x;
+    const int t = st->t, Lmax = st->Lmax;
+    if (t < 0 || t >= Lmax) return;                           // (uniform)
+    const bool sample = st->inv_tau > 0.f;                    // (uniform) temperature and seed come from the state, as t does: one
+    const float inv_tau = sample ? st->inv_tau : 1.0f;        // captured step serves every seed and temperature
+    const unsigned k0 = st->seed_lo, k1 = st->seed_hi;
+    float* lrow = step_logits ? step_logits + ((size_t)b * Lmax + t) * V : nullptr;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    const int nchunk = (V + 7) >> 3;                          // 8 columns at a time (ld % 8 == 0: the chunk lies inside the row)
+    for (int c = threadIdx.x; c < nchunk; c += SEL_THREADS) {
+        const f32x8 x8 = IO<DT>::load8(logits, (size_t)b * ld + 8 * c);
+        const float x[8] = {x8.lo.x, x8.lo.y, x8.lo.z, x8.lo.w, x8.hi.x, x8.hi.y, x8.hi.z, x8.hi.w};
+        float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (sample) {                                         // (uniform)
+            const U4 r0 = philox4x32((unsigned)(2 * c), (unsigned)b, (unsigned)t, 0x47454e53u, k0, k1);
+            const U4 r1 = philox4x32((unsigned)(2 * c + 1), (unsigned)b, (unsigned)t, 0x47454e53u, k0, k1);
+            g[0] = gen_gumbel_from_bits(r0.x); g[1] = gen_gumbel_from_bits(r0.y); g[2] = gen_gumbel_from_bits(r0.z); g[3] = gen_gumbel_from_bits(r0.w);
+            g[4] = gen_gumbel_from_bits(r1.x); g[5] = gen_gumbel_from_bits(r1.y); g[6] = gen_gumbel_from_bits(r1.z); g[7] = gen_gumbel_from_bits(r1.w);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int v = 8 * c + e;
+            if (v < V) {
+                if (lrow) lrow[v] = x[e];
+                const float s = x[e] * inv_tau + g[e];
+                if (sel_better(s, v, bv, bi)) { bv = s; bi = v; }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ov = __shfl_xor(bv, m, WAVE);
+        const int oi = __shfl_xor(bi, m, WAVE);
+        if (sel_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if ((threadIdx.x & 63) == 0) { wv[threadIdx.x >> 6] = bv; wi[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < SEL_THREADS / WAVE; ++w)
+            if (sel_better(wv[w], wi[w], bv, bi)) { bv = wv[w]; bi = wi[w]; }
+        const int choice = bi == 0x7fffffff ? 0 : bi;          // (a row of NaNs)
+        if (t + 1 < Lmax && t + 1 >= st->P) {                  // (inside the prompt the token that is there is kept)
+            int64_t* dst = ids + (size_t)b * Lmax + t + 1;
+            if (finished[b]) {
+                *dst = st->pad_id;
+            } else {
+                *dst = choice;
+                if (choice == st->eos_id) { finished[b] = 1; lengths[b] = t + 2; }
+            }
+        }
+    }
+}
+
+__global__ void gen_advance_kernel(GenState* st) { st->t += 1; }
+
+__global__ void gen_gumbel_debug_kernel(const unsigned* __restrict__ bits, int64_t n, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = gen_gumbel_from_bits(bits[i]);
+}
+
+}  // namespace kvq
+
+using namespace kvq;
+
+extern "C" {
+
+int kvq_gen_embed(const void* state, const int64_t* ids, const void* word, const void* pos, const void* type_row, const float* gamma,
+                  const float* beta, int B, int H, int64_t V, int pos_rows, float eps, int io_dtype, void* out, void* stream) {
+    KVQ_REQUIRE(state && ids && word && pos && type_row && gamma && beta && out, "kvq_gen_embed: null pointer argument");
+    KVQ_REQUIRE(B > 0 && H > 0 && V > 0 && pos_rows > 0, "kvq_gen_embed: B, H, V and pos_rows must be positive");
+    KVQ_REQUIRE(H % 4 == 0 && H <= 64 * 4 * GEN_LN_MAX_PER_LANE, "kvq_gen_embed: H=%d must be a multiple of 4 and <= 4096", H);
+    KVQ_REQUIRE(io_dtype == KVQ_F32 || io_dtype == KVQ_BF16, "kvq_gen_embed: unsupported io dtype %d", io_dtype);
+    KVQ_REQUIRE(((uintptr_t)state & 7) == 0 && ((uintptr_t)ids & 7) == 0, "kvq_gen_embed: 8-byte aligned state and ids required");
+    KVQ_REQUIRE((((uintptr_t)word | (uintptr_t)pos | (uintptr_t)type_row | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out) & 15) == 0
+                    && ((size_t)H * (io_dtype == KVQ_BF16 ? 2 : 4)) % 8 == 0,
+                "kvq_gen_embed: 16-byte aligned tables, LayerNorm weights and output required");
+    hipStream_t s = (hipStream_t)stream;
+    const GenState* gs = reinterpret_cast<const GenState*>(state);
+    dim3 grid((unsigned)((B + 3) / 4));
+    auto with_dt = [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        // (H, io dtype) -> <DT, PER> as ln_dispatch of csrc/kvq_ln.hip maps them: the same chunks per lane, the same sums
+        if (H <= 768)
+            hipLaunchKernelGGL((gen_embed_kernel<DT, 3>), grid, dim3(256), 0, s, gs, ids, word, pos, type_row, gamma, beta, B, H, V, pos_rows, eps, out);
+        else if (H <= 1024)
+            hipLaunchKernelGGL((gen_embed_kernel<DT, 4>), grid, dim3(256), 0, s, gs, ids, word, pos, type_row, gamma, beta, B, H, V, pos_rows, eps, out);
+        else
+            hipLaunchKernelGGL((gen_embed_kernel<DT, GEN_LN_MAX_PER_LANE>), grid, dim3(256), 0, s, gs, ids, word, pos, type_row, gamma, beta, B, H, V,
+                               pos_rows, eps, out);
+    };
+    if (io_dtype == KVQ_F32) with_dt(std::integral_constant<int, KVQ_F32>());
+    else with_dt(std::integral_constant<int, KVQ_BF16>());
+    return check_launch("gen_embed_kernel");
+}
+
+int kvq_gen_attn(const void* state, const void* q, int64_t ldq, const void* k_new, const void* v_new, int64_t ld_new, void* kv,
+                 int64_t ld_kv, int64_t kv_sentence_stride, int B, int nh, int append, int n_keys, int Smax, int io_dtype, void* out,
+                 int64_t ldo, void* stream) {
+    KVQ_REQUIRE(state && q && kv && out, "kvq_gen_attn: null pointer argument");
+    KVQ_REQUIRE(io_dtype == KVQ_F32 || io_dtype == KVQ_BF16, "kvq_gen_attn: unsupported io dtype %d", io_dtype);
+    KVQ_REQUIRE(B > 0 && nh > 0 && (int64_t)B * nh < (1ll << 31), "kvq_gen_attn: B and nh must be positive (B=%d nh=%d)", B, nh);
+    const int64_t W = (int64_t)nh * 64;                                    // columns of q, of the keys and of the values
+    const int epl = io_dtype == KVQ_BF16 ? 8 : 4;                          // elements of a 16-byte access
+    KVQ_REQUIRE(ldq >= W && ldo >= W && ld_kv >= 2 * W, "kvq_gen_attn: leading dimension below the %lld columns of %d heads", (long long)W, nh);
+    KVQ_REQUIRE(ldq % epl == 0 && ldo % epl == 0 && ld_kv % epl == 0 && kv_sentence_stride % epl == 0,
+                "kvq_gen_attn: every stride must be a multiple of 16 bytes");
+    KVQ_REQUIRE((((uintptr_t)q | (uintptr_t)kv | (uintptr_t)out) & 15) == 0 && ((uintptr_t)state & 7) == 0,
+                "kvq_gen_attn: 16-byte aligned q, kv and out (8-byte aligned state) required");
+    if (append) {
+        KVQ_REQUIRE(k_new && v_new && (((uintptr_t)k_new | (uintptr_t)v_new) & 15) == 0 && ld_new >= W && ld_new % epl == 0,
+                    "kvq_gen_attn: append needs 16-byte aligned k_new / v_new rows of at least %lld columns", (long long)W);
+        KVQ_REQUIRE(Smax >= 1 && Smax <= GEN_MAX_KEYS, "kvq_gen_attn: Smax=%d outside 1..%d", Smax, GEN_MAX_KEYS);
+        KVQ_REQUIRE(kv_sentence_stride >= (int64_t)Smax * ld_kv, "kvq_gen_attn: a sentence of the cache holds fewer than Smax=%d rows", Smax);
+    } else {
+        KVQ_REQUIRE(n_keys >= 1 && n_keys <= GEN_MAX_KEYS, "kvq_gen_attn: n_keys=%d outside 1..%d", n_keys, GEN_MAX_KEYS);
+        KVQ_REQUIRE(kv_sentence_stride >= (int64_t)n_keys * ld_kv, "kvq_gen_attn: a sentence holds fewer than n_keys=%d rows", n_keys);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const GenState* gs = reinterpret_cast<const GenState*>(state);
+    dim3 grid((unsigned)(B * nh));
+    if (io_dtype == KVQ_F32)
+        hipLaunchKernelGGL(gen_attn_kernel<KVQ_F32>, grid, dim3(64), 0, s, gs, q, ldq, k_new, v_new, ld_new, kv, ld_kv, kv_sentence_stride, nh,
+                           append, n_keys, Smax, out, ldo);
+    else
+        hipLaunchKernelGGL(gen_attn_kernel<KVQ_BF16>, grid, dim3(64), 0, s, gs, q, ldq, k_new, v_new, ld_new, kv, ld_kv, kv_sentence_stride, nh,
+                           append, n_keys, Smax, out, ldo);
+    return check_launch("gen_attn_kernel");
+}
+
+int kvq_gen_select(const void* state, const void* logits, int64_t ld, int V, int B, int io_dtype, int64_t* ids, int32_t* finished, int32_t* lengths, float* step_logits, void* stream) {
+    KVQ_REQUIRE(state && logits && ids && finished && lengths, "kvq_gen_select: null pointer argument");
+    KVQ_REQUIRE(io_dtype == KVQ_F32 || io_dtype == KVQ_BF16, "kvq_gen_select: unsupported io dtype %d", io_dtype);
+    KVQ_REQUIRE(B > 0 && V > 0 && ld >= V, "kvq_gen_select: B, V must be positive and ld >= V (B=%d V=%d ld=%lld)", B, V, (long long)ld);
+    KVQ_REQUIRE(ld % 8 == 0 && ((uintptr_t)logits & 15) == 0, "kvq_gen_select: ld %% 8 == 0 and 16-byte aligned logits required");
+    KVQ_REQUIRE(((uintptr_t)state & 7) == 0 && ((uintptr_t)ids & 7) == 0 && (((uintptr_t)finished | (uintptr_t)lengths | (uintptr_t)step_logits) & 3) == 0,
+                "kvq_gen_select: misaligned state, ids, finished, lengths or step_logits");
+    hipStream_t s = (hipStream_t)stream;
+    const GenState* gs = reinterpret_cast<const GenState*>(state);
+    if (io_dtype == KVQ_F32)
+        hipLaunchKernelGGL(gen_select_kernel<KVQ_F32>, dim3((unsigned)B), dim3(SEL_THREADS), 0, s, gs, logits, ld, V, ids, finished, lengths,
+                           step_logits);
+    else
+        hipLaunchKernelGGL(gen_select_kernel<KVQ_BF16>, dim3((unsigned)B), dim3(SEL_THREADS), 0, s, gs, logits, ld, V, ids, finished, lengths,
+                           step_logits);
+    return check_launch("gen_select_kernel");
+}
+
+int kvq_gen_advance(void* state, void* stream) {
+    KVQ_REQUIRE(state && ((uintptr_t)state & 7) == 0, "kvq_gen_advance: null / misaligned generation state");
+    hipLaunchKernelGGL(gen_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (GenState*)state);
+    return check_launch("gen_advance_kernel");
+}
+
+int kvq_gen_gumbel_debug(const uint32_t* bits, int64_t n, float* out, void* stream) {
+    KVQ_REQUIRE(bits && out && n > 0 && n < (1ll << 31), "kvq_gen_gumbel_debug: bad argument");
+    KVQ_REQUIRE((((uintptr_t)bits | (uintptr_t)out) & 3) == 0, "kvq_gen_gumbel_debug: misaligned buffers");
+    hipLaunchKernelGGL(gen_gumbel_debug_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bits, n, out);
+    return check_launch("gen_gumbel_debug_kernel");
+}
+
+}  // extern "C"

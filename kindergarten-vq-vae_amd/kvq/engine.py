@@ -654,6 +654,7 @@ class TrainEngine:
         # small f32 parameters outside the flat buffers (codebook, Gumbel projection / embedding): own gradient + Adam state
         self.aux = []
         self._bufs = {}
+        self._gen_cache = {}              # generate(): buffers and captured step per (B, Se, max_length, want_logits)
 
         def add_aux(p, name):
             a = dict(name=name, p=p, g=torch.zeros_like(p.data), m=torch.zeros_like(p.data), v=torch.zeros_like(p.data),
@@ -1779,8 +1780,9 @@ class TrainEngine:
     # ------------------------------------------------------------------------------------------------------------
     _TRAVERSE_CHUNK = 256               # variants per decode of traverse_codes
 
-    def _latent_call(self, what):
-        """What encode / decode / decode_codes / traverse_codes refuse, before anything is launched."""
+    def _latent_call(self, what, refresh=True):
+        """What encode / decode / decode_codes / traverse_codes refuse, before anything is launched.  refresh=False: the refusals
+        alone (generate runs them in front of its argument checks, which read the prompt's range from the device)."""
         if self._cap is not None or torch.cuda.is_current_stream_capturing():
             raise KvqError(f"TrainEngine.{what} is an eager call: not under graph capture")
         if self.group is not None or self._dp:
@@ -1788,6 +1790,8 @@ class TrainEngine:
         if self.fp8:
             raise KvqError(f"TrainEngine.{what}: not on an fp8 engine -- its GEMMs read fp8 copies that the kernel producing an "
                            f"activation writes beside it, and a latent handed in from outside has no such producer-written copy")
+        if not refresh:
+            return
         self.refresh_if_params_changed()
         if getattr(self, "_epack", None) is not None:
             self._E_version = None
@@ -1875,10 +1879,228 @@ class TrainEngine:
         self._latent_call("decode_codes")
         return self.decode(self.codes_to_latents(indices), dec_ids, dec_mask, target_ids=target_ids, want_logits=want_logits)
 
-    def traverse_codes(self, enc_ids, enc_mask, sentence, position, dec_ids=None, dec_mask=None, factor=0):
+    # ------------------------------------------------------------------------------------------------------------
+    # free-running generation: the decoder one position at a time over a key/value cache
+    # ------------------------------------------------------------------------------------------------------------
+    _GEN_GRAPHS_KEPT = 8                # captured steps kept per engine (one per shape / choice rule), oldest dropped first
+
+    @staticmethod
+    def _check_generate(latents, max_length, prompt_ids, H, dtype, dev, pos_rows, temperature, **ids_kw):
+        """The argument checks of generate() that need no device: every refusal happens before any launch."""
+        if not torch.is_tensor(latents) or latents.dim() != 3 or latents.shape[2] != H:
+            raise KvqError(f"TrainEngine.generate: latents must be [B, Se, {H}], got "
+                           f"{tuple(latents.shape) if torch.is_tensor(latents) else type(latents).__name__}")
+        if latents.dtype != dtype or latents.device != dev or not latents.is_contiguous():
+            raise KvqError(f"TrainEngine.generate: latents must be contiguous {dtype} on {dev}, got {latents.dtype} on {latents.device}")
+        if latents.shape[0] < 1 or latents.shape[1] < 1:
+            raise KvqError(f"TrainEngine.generate: empty latents {tuple(latents.shape)}")
+        TrainEngine._check_generate_call(latents.shape[0], max_length, prompt_ids, dev, pos_rows, temperature, **ids_kw)
+
+    @staticmethod
+    def _check_generate_call(B, max_length, prompt_ids, dev, pos_rows, temperature, V=None, eos_id=None, pad_id=None, seed=0):
+        """The part of _check_generate that does not look at the latents (generate_codes runs it before the codebook lookup).
+        V (the vocabulary size): eos_id, pad_id and every prompt id must be token ids; the prompt's range is one reduction over
+        [B, P] and a host read, the only device work of the checks."""
+        if isinstance(max_length, bool) or not isinstance(max_length, int) or max_length < 1:
+            raise KvqError(f"TrainEngine.generate: max_length must be a positive int, got {max_length!r}")
+        if max_length > pos_rows:
+            raise KvqError(f"TrainEngine.generate: max_length {max_length} above the decoder's position table ({pos_rows} rows)")
+        if not torch.is_tensor(prompt_ids) or prompt_ids.dtype != torch.int64 or prompt_ids.dim() != 2 \
+                or prompt_ids.shape[0] != B or prompt_ids.shape[1] < 1:
+            raise KvqError(f"TrainEngine.generate: prompt_ids must be int64 [B, P] with B = {B} and P >= 1 (e.g. a column "
+                           f"of start ids), got {tuple(prompt_ids.shape) if torch.is_tensor(prompt_ids) else type(prompt_ids).__name__}"
+                           + (f" {prompt_ids.dtype}" if torch.is_tensor(prompt_ids) else ""))
+        if prompt_ids.device != dev:
+            raise KvqError(f"TrainEngine.generate: prompt_ids must be on {dev}, got {prompt_ids.device}")
+        if prompt_ids.shape[1] > max_length:
+            raise KvqError(f"TrainEngine.generate: a prompt of {prompt_ids.shape[1]} tokens does not fit max_length {max_length}")
+        if not (float(temperature) >= 0.0) or float(temperature) == float("inf") or (temperature > 0 and 1.0 / float(temperature) > 3.0e38):
+            raise KvqError(f"TrainEngine.generate: temperature must be finite and >= 0 (0 = greedy; 1 / temperature an f32), got {temperature!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64):
+            raise KvqError(f"TrainEngine.generate: seed must be an int in [0, 2^64), got {seed!r}")
+        for name, v in (("eos_id", eos_id), ("pad_id", pad_id)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 0 or (V is not None and v >= V)):
+                raise KvqError(f"TrainEngine.generate: {name} must be None or a token id (an int in [0, {V if V is not None else 'V'})), got {v!r}")
+        if V is not None:
+            lo, hi = (int(x) for x in torch.aminmax(prompt_ids))
+            if lo < 0 or hi >= V:
+                raise KvqError(f"TrainEngine.generate: prompt_ids hold ids outside [0, {V}) (smallest {lo}, largest {hi})")
+
+    def _gen_step(self, g):
+        """One position: the decoder layer schedule of _fb_gen on [Bp, H] rows, the token at column t in, the token at t + 1 out.
+        Launches only (no host read): the body of the captured graph, and what graph=False runs max_length - 1 times."""
+        fl, H, nh, dcfg = self.flat, self.H, self.nh, self.dcfg
+        eps, st = dcfg.layer_norm_eps, g["state"]
+        x = nnops.gen_embed(st, g["ids"], fl.w("dec.emb.word"), fl.w("dec.emb.pos"), fl.w("dec.emb.type")[0], fl.w32("dec.emb.ln.w"),
+                            fl.w32("dec.emb.ln.b"), eps)
+        for i in range(self.n_dec_layers):
+            pre = f"dec.{i}.sa."
+            qkv = self._linear(x, None, None, fused=([pre + "q.w", pre + "k.w", pre + "v.w"], [pre + "q.b", pre + "k.b", pre + "v.b"]))
+            ctx = nnops.gen_attn_self(st, qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], g["cache"][i], nh)
+            x = self._dense_residual_ln(ctx, pre + "o.w", pre + "o.b", x, pre + "ln.w", pre + "ln.b", eps, 0.0, 0)[0]
+            pre = f"dec.{i}.ca."
+            q = self._linear(x, pre + "q.w", pre + "q.b")
+            ctx = nnops.gen_attn_cross(st, q, g["kv"][i], g["Se"], nh)
+            x = self._dense_residual_ln(ctx, pre + "o.w", pre + "o.b", x, pre + "ln.w", pre + "ln.b", eps, 0.0, 0)[0]
+            pre = f"dec.{i}."
+            a = self._linear_gelu(x, pre + "f1.w", pre + "f1.b")[1]
+            x = self._dense_residual_ln(a, pre + "f2.w", pre + "f2.b", x, pre + "ln2.w", pre + "ln2.b", eps, 0.0, 0)[0]
+        ta = self._linear_gelu(x, "head.t.w", "head.t.b")[1]
+        hN = nnops.ln_fwd(ta, None, fl.w32("head.ln.w"), fl.w32("head.ln.b"), eps, save_pre=False)[0]
+        Wv = fl.w("dec.emb.word", rows=self.Vp)
+        bv = fl.shadow[fl.seg["head.bias"][0]: fl.seg["head.bias"][0] + self.Vp]
+        logits = self._linear(hN, None, None, Wb=(Wv, bv), key="dec.emb.word")                      # [Bp, Vp]
+        nnops.gen_select(st, logits, self.V, g["ids"], g["finished"], g["lengths"], g["step_logits"])      # (temperature, seed: in the state)
+        nnops.gen_advance(st)
+
+    def _gen_buffers(self, B, Se, L, want_logits, graph):
+        """The buffers of one (B, Se, max_length) -- allocated once, the same addresses in every call -- and, with graph, the captured
+        step: position, prompt length, end token, temperature and seed all live in the device state, so one graph serves every call
+        of the shape.  Kept per engine, the oldest of more than _GEN_GRAPHS_KEPT is dropped."""
+        cache = self._gen_cache
+        key = (B, Se, L, bool(want_logits), self.flat.shadow.data_ptr())
+        g = cache.get(key)
+        if g is None:
+            dev, H, Bp, nl = self.dev, self.H, _round_up(B, 8), self.n_dec_layers
+            g = dict(B=B, Bp=Bp, Se=Se, L=L, graph=None, replays=0,
+                     state=nnops.new_gen_state(dev, 0, 1, L, None, 0),
+                     ids=torch.zeros((Bp, L), dtype=torch.int64, device=dev),
+                     finished=torch.zeros(Bp, dtype=torch.int32, device=dev), lengths=torch.zeros(Bp, dtype=torch.int32, device=dev),
+                     cache=[torch.zeros((Bp, L, 2 * H), dtype=self.dtype, device=dev) for _ in range(nl)],
+                     lat=torch.zeros((Bp, Se, H), dtype=self.dtype, device=dev),
+                     step_logits=torch.zeros((Bp, L, self.V), dtype=torch.float32, device=dev) if want_logits else None)
+            if self._cakv_batched:
+                g["kv_all"] = torch.empty((Bp * Se, nl * 2 * H), dtype=self.dtype, device=dev)
+                g["kv"] = [g["kv_all"][:, 2 * H * i: 2 * H * (i + 1)] for i in range(nl)]
+            else:
+                g["kv"] = [torch.empty((Bp * Se, 2 * H), dtype=self.dtype, device=dev) for _ in range(nl)]
+            while len(cache) >= self._GEN_GRAPHS_KEPT:
+                cache.pop(next(iter(cache)))
+            cache[key] = g
+        if graph and g["graph"] is None and L > 1:
+            self._gen_step(g)                       # once eagerly: whatever a library allocates on first use happens outside the capture
+            g["graph"] = self._gen_capture(g)
+        return g
+
+    def _gen_capture(self, g):
+        """The step as ONE hipGraph, captured on a single stream (no parallel branches); kernel nodes only (gen_census)."""
+        import gc
+        dev = self.dev
+        graph = torch.cuda.CUDAGraph(keep_graph=True)
+        side = torch.cuda.Stream(device=dev)
+        gc_was_on = gc.isenabled()
+        try:
+            gc.collect()
+            gc.disable()                            # (as _StepGraphs: no HIP object may be destroyed while this thread captures)
+            torch.cuda.synchronize(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                graph.capture_begin(capture_error_mode="thread_local")
+                try:
+                    self._gen_step(g)
+                finally:
+                    graph.capture_end()
+        finally:
+            if gc_was_on:
+                gc.enable()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        return graph
+
+    def gen_census(self):
+        """Per captured generation step: {kind: nodes} (kvq_graph_census), as _StepGraphs.node_census."""
+        import ctypes
+        kinds = ("kernel", "memset", "memcpy", "empty", "event", "other")
+        out = []
+        for g in self._gen_cache.values():
+            if g["graph"] is not None:
+                counts = (ctypes.c_int64 * len(kinds))()
+                check(lib().kvq_graph_census(g["graph"].raw_cuda_graph(), counts), "kvq_graph_census")
+                out.append(dict(zip(kinds, (int(c) for c in counts))))
+        return out
+
+    def generate(self, latents, max_length, prompt_ids, eos_id=None, pad_id=None, temperature=0.0, seed=0, quantize=False,
+                 want_logits=False, graph=True):
+        """Free-running generation from a latent: the decoder sees only the prompt and what it has written itself.  latents
+        [B, Se, H] as decode() takes them; prompt_ids [B, P] int64 (P >= 1, e.g. a column of start ids) fills columns 0 .. P-1, the
+        recurrence  ids[:, t + 1] = choose(logits(latents, ids[:, :t + 1])[t])  the rest up to max_length.  choose: the first arg-max
+        (temperature 0) or a draw from softmax(logits / temperature) (kvq_gen_select; `seed`).  A sentence that chooses eos_id is
+        finished: lengths = its tokens including the end token, pad_id (default: the embeddings' padding_idx, else 0) behind it.
+        One decoder token per sentence and position over a key/value cache (csrc/kvq_generate.hip), no host read inside the loop;
+        graph=True replays one captured step max_length - 1 times, graph=False launches it eagerly -- the same bits.
+        Returns dict(ids [B, max_length], lengths [B], finished [B] bool [, logits [B, max_length - 1, V] f32: row t = what chose
+        column t + 1] [, indices]).  Meaningful for a model trained to predict the NEXT token (DECODER_NEXT_TOKEN); a model trained
+        on the reference's unshifted loss reproduces its input token by construction."""
+        self._latent_call("generate", refresh=False)
+        self._check_generate(latents, max_length, prompt_ids, self.H, self.dtype, self.dev, int(self.dcfg.max_position_embeddings), temperature,
+                             V=self.V, eos_id=eos_id, pad_id=pad_id, seed=seed)
+        if quantize and not self.has_vq:
+            raise KvqError("TrainEngine.generate: quantize=True, but the model has no quantiser")
+        B, Se, _ = latents.shape
+        L, P = int(max_length), prompt_ids.shape[1]
+        self._seq_limit("generate", Se, L)
+        self._latent_call("generate")               # (refuses first, then brings the flat buffers up to date: the first launches)
+        res = {}
+        if quantize:                                # the quantiser in evaluation mode, as decode(quantize=True)
+            one = torch.zeros((B, 1), dtype=torch.int64, device=self.dev)
+            q = self.forward_backward(None, None, training=False, compute_grads=False, dec_ids=one, dec_mask=torch.ones_like(one),
+                                      quantizer_training=False, stop_after_quantizer=True, want_latents=True, latents=latents)
+            latents, res["indices"] = q["z_q"].reshape(B, Se, self.H), q["indices"]
+        with torch.no_grad():
+            g = self._gen_buffers(B, Se, L, want_logits, graph)
+            Bp = g["Bp"]
+            # ---- once per call: the cross-attention keys | values of every layer, the state ----
+            g["lat"][:B].copy_(latents)
+            lat = g["lat"].view(Bp * Se, self.H)
+            fl = self.flat
+            if self._cakv_batched:
+                g["kv_all"].copy_(self._linear(lat, None, None, Wb=(fl.fused(self._cakv_w, fl.shadow), fl.fused(self._cakv_b, fl.shadow)),
+                                               key=self._cakv_w[0]))
+            else:
+                for i in range(self.n_dec_layers):
+                    pre = f"dec.{i}.ca."
+                    g["kv"][i].copy_(self._linear(lat, None, None, fused=([pre + "k.w", pre + "v.w"], [pre + "k.b", pre + "v.b"])))
+            pad = (self._pad_idx if self._pad_idx is not None else 0) if pad_id is None else int(pad_id)
+            g["state"].copy_(torch.tensor(nnops.gen_state_words(0, P, L, eos_id, pad, float(temperature), int(seed) if temperature > 0 else 0),
+                                          dtype=torch.int32), non_blocking=False)
+            g["ids"].fill_(pad)
+            g["ids"][:B, :P].copy_(prompt_ids)
+            g["finished"].zero_()
+            g["finished"][B:].fill_(1)              # the rows that pad the batch to a multiple of 8: computed, never reported
+            g["lengths"].fill_(L)
+            if g["step_logits"] is not None:
+                g["step_logits"].zero_()
+            # ---- per position ----
+            for _ in range(L - 1):
+                if graph:
+                    g["graph"].replay()
+                else:
+                    self._gen_step(g)
+            g["replays"] += (L - 1) if graph else 0
+            res.update(ids=g["ids"][:B].clone(), lengths=g["lengths"][:B].long(), finished=g["finished"][:B] != 0)
+            if want_logits:
+                res["logits"] = g["step_logits"][:B, :L - 1].clone()
+        return res
+
+    def generate_codes(self, indices, max_length, prompt_ids, **kw):
+        """generate() of the codebook rows of `indices` [B, Se] / [B, Se, G] int64: as decode_codes is to decode."""
+        if kw.get("quantize"):
+            raise KvqError("TrainEngine.generate_codes: the latents are codebook rows already (quantize=True has nothing to do)")
+        self._latent_call("generate_codes", refresh=False)
+        rows = self._code_rows("generate_codes", indices)
+        self._check_generate_call(rows.shape[0], max_length, prompt_ids, self.dev, int(self.dcfg.max_position_embeddings),
+                                  kw.get("temperature", 0.0), V=self.V, eos_id=kw.get("eos_id"), pad_id=kw.get("pad_id"), seed=kw.get("seed", 0))
+        self._seq_limit("generate", rows.shape[1], max_length)
+        self._latent_call("generate_codes")         # every refusal above and in here comes before the lookup's launch
+        return self.generate(self.codes_to_latents(rows), max_length, prompt_ids, **kw)
+
+    def traverse_codes(self, enc_ids, enc_mask, sentence, position, dec_ids=None, dec_mask=None, factor=0, free_running=False,
+                       max_length=None, start_id=None):
         """Every code at one place of one sentence: encodes the batch, takes sentence `sentence`'s own index rows [Se, G], builds the
         K variants that differ from them only at (position, factor) -- variant k carries code k there -- and decodes them with
         that sentence's decoder ids (default: its encoder ids), at most 256 variants per launch sequence.
+        free_running=True: the variants are GENERATED (generate_codes, greedy) from start_id (default: the first decoder id of the
+        sentence) up to max_length (default: the decoder ids' length) instead of decoded against the sentence's own ids.
         Returns dict(recon_ids [K, Sd], own_code (int), changed [K, Sd] bool: tokens that differ from the own code's row)."""
         self._latent_call("traverse_codes")
         if self.vq_kind not in ("VectorQuantizer", "MultiVectorQuantizer"):
@@ -1900,6 +2122,12 @@ class TrainEngine:
         recon = []
         for k0 in range(0, K, self._TRAVERSE_CHUNK):
             n = min(self._TRAVERSE_CHUNK, K - k0)
+            if free_running:
+                start = int(d_ids[int(sentence), 0].item()) if start_id is None else int(start_id)
+                out = self.generate_codes(rows[k0:k0 + n], int(d_ids.shape[1] if max_length is None else max_length),
+                                          torch.full((n, 1), start, dtype=torch.int64, device=self.dev))
+                recon.append(out["ids"])
+                continue
             out = self.decode_codes(rows[k0:k0 + n], d_ids[int(sentence)].unsqueeze(0).expand(n, -1).contiguous(),
                                     d_mask[int(sentence)].unsqueeze(0).expand(n, -1).contiguous())
             recon.append(out["recon_ids"])

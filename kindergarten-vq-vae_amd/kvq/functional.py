@@ -401,3 +401,18 @@ def fused_cross_entropy(logits: torch.Tensor, target: torch.Tensor, inplace_back
         raise _ffi.KvqError(f"fused_cross_entropy: ignore_index must be None or an int, got {ignore_index!r}")
     loss, acc, pred = _FusedCE.apply(logits.reshape(-1, V), target, inplace_backward, ignore_index)
     return loss, acc, pred.reshape(shape)
+
+
+def shift_right(ids: torch.Tensor, start_id: int) -> torch.Tensor:
+    """[start_id, ids[..., :-1]] along the last dimension: the decoder input of a next-token objective, whose logits at position t
+    are scored against ids[..., t] without having seen it (DECODER_NEXT_TOKEN).  The same call with start_id = 1
+    shifts the attention mask: the start token is attended, the padding of a ragged batch moves one place right with its tokens
+    and the last real token (or pad) of every row falls off.  ids is not modified."""
+    if not torch.is_tensor(ids) or ids.dim() < 1 or ids.shape[-1] < 1:
+        raise _ffi.KvqError("shift_right: ids must be a tensor with a non-empty last dimension")
+    if isinstance(start_id, bool) or not isinstance(start_id, int):
+        raise _ffi.KvqError(f"shift_right: start_id must be an int, got {start_id!r}")
+    out = torch.empty_like(ids)
+    out[..., :1] = start_id
+    out[..., 1:] = ids[..., :-1]
+    return out

@@ -507,6 +507,146 @@ def accum_advance(state, A):
     check(lib().kvq_accum_advance(_accum_ptr(state), int(A), stream_ptr()), "kvq_accum_advance")
 
 
+# ---- free-running generation (include/kvq.h "free-running generation"; csrc/kvq_generate.hip) -------------------------------------
+GEN_MAX_KEYS = 128
+
+
+def new_gen_state(device, t=0, prompt_len=1, max_length=1, eos_id=None, pad_id=0, temperature=0.0, seed=0):
+    """32 bytes: struct { int32 t, P, Lmax, eos_id, pad_id; uint32 seed_lo, seed_hi; float inv_tau; } of include/kvq.h.
+    eos_id None = no end token (-1); temperature 0 = greedy (inv_tau 0)."""
+    return torch.tensor(gen_state_words(t, prompt_len, max_length, eos_id, pad_id, temperature, seed), dtype=torch.int32).to(device)
+
+
+def _i32(u):
+    """the int32 with the bits of the uint32 u"""
+    u &= 0xFFFFFFFF
+    return u - (1 << 32) if u >= (1 << 31) else u
+
+
+def gen_state_words(t, prompt_len, max_length, eos_id, pad_id, temperature=0.0, seed=0):
+    """The eight int32 words of a generation state.  temperature > 0: the words carry the f32 bits of 1 / temperature and the
+    64-bit Philox key; 0: greedy."""
+    import struct
+    if not (float(temperature) >= 0.0) or float(temperature) == float("inf"):
+        raise KvqError(f"a generation state takes a finite temperature >= 0 (0 = greedy), got {temperature!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < (1 << 64):
+        raise KvqError(f"a generation state takes a seed in [0, 2^64), got {seed!r}")
+    inv = 1.0 / float(temperature) if temperature > 0 else 0.0
+    if inv > 3.0e38:                         # (no f32 holds it)
+        raise KvqError(f"a generation state cannot hold 1 / temperature for temperature {temperature!r}")
+    bits = struct.unpack("<I", struct.pack("<f", inv))[0]
+    return [int(t), int(prompt_len), int(max_length), -1 if eos_id is None else int(eos_id), int(pad_id), _i32(seed), _i32(seed >> 32),
+            _i32(bits)]
+
+
+def _gen_ptr(state):
+    if not torch.is_tensor(state) or state.dtype != torch.int32 or state.numel() != 8 or not state.is_contiguous():
+        raise KvqError("a generation state is new_gen_state()'s tensor (8 x int32)")
+    require_gpu(state)
+    return state.data_ptr()
+
+
+def read_gen_state(state):
+    """dict(t, P, Lmax, eos_id, pad_id, seed, inv_tau) -- synchronises; for tests."""
+    import struct
+    _gen_ptr(state)
+    w = state.cpu().tolist()
+    return dict(t=w[0], P=w[1], Lmax=w[2], eos_id=w[3], pad_id=w[4], seed=(w[5] & 0xFFFFFFFF) | ((w[6] & 0xFFFFFFFF) << 32),
+                inv_tau=struct.unpack("<f", struct.pack("<I", w[7] & 0xFFFFFFFF))[0])
+
+
+def gen_embed(state, ids, word, pos, type_row, gamma, beta, eps, out=None):
+    """out [B, H] = LayerNorm(word[ids[b, t]] + pos[t] + type_row), t read from the state on the device: the bits of
+    embed_ln_fwd's row for the same token at the same position (no dropout)."""
+    require_gpu(ids, word, pos, type_row, gamma, beta)
+    if ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise KvqError("kvq.nnops.gen_embed: ids must be a contiguous int64 [B, Lmax] tensor")
+    B, H = ids.shape[0], word.shape[1]
+    if out is None:
+        out = torch.empty((B, H), dtype=word.dtype, device=word.device)
+    check(lib().kvq_gen_embed(_gen_ptr(state), ids.data_ptr(), word.data_ptr(), pos.data_ptr(), type_row.data_ptr(), gamma.data_ptr(),
+                              beta.data_ptr(), B, H, word.shape[0], pos.shape[0], float(eps), io_dtype_of(word), out.data_ptr(), stream_ptr()),
+          "kvq_gen_embed")
+    return out
+
+
+def _gen_rows(who, x, name):
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise KvqError(f"kvq.nnops.{who}: {name} must be 2-D with unit column stride")
+    return x.stride(0)
+
+
+def gen_attn_self(state, q, k_new, v_new, cache, nh, out=None):
+    """One query row per (sentence, head) against the cache [B, Smax, 2 nh 64]: this step's k_new | v_new rows (column slices of the
+    fused projection, [B, nh 64] each, one row stride) are stored to row t first, then rows 0 .. t are attended.  t: from the state."""
+    require_gpu(q, k_new, v_new, cache)
+    B, W = q.shape[0], nh * 64
+    ldq, ldn = _gen_rows("gen_attn_self", q, "q"), _gen_rows("gen_attn_self", k_new, "k_new")
+    if _gen_rows("gen_attn_self", v_new, "v_new") != ldn or k_new.shape != (B, W) or v_new.shape != (B, W) or q.shape[1] != W:
+        raise KvqError(f"kvq.nnops.gen_attn_self: q, k_new, v_new must be [B, {W}] and k_new, v_new share a row stride")
+    if cache.dim() != 3 or cache.shape[0] != B or cache.shape[2] != 2 * W or not cache.is_contiguous() or cache.dtype != q.dtype:
+        raise KvqError(f"kvq.nnops.gen_attn_self: the cache must be a contiguous [B, Smax, {2 * W}] tensor of q's dtype")
+    if out is None:
+        out = torch.empty((B, W), dtype=q.dtype, device=q.device)
+    check(lib().kvq_gen_attn(_gen_ptr(state), q.data_ptr(), ldq, k_new.data_ptr(), v_new.data_ptr(), ldn, cache.data_ptr(), cache.stride(1),
+                             cache.stride(0), B, nh, 1, 0, cache.shape[1], io_dtype_of(q), out.data_ptr(), _gen_rows("gen_attn_self", out, "out"),
+                             stream_ptr()), "kvq_gen_attn")
+    return out
+
+
+def gen_attn_cross(state, q, kv, n_keys, nh, out=None):
+    """The same against n_keys given rows per sentence: kv [B * n_keys, >= 2 nh 64] = keys | values (a column slice of the all-layer
+    projection of the latent is fine: its row stride is used).  No mask."""
+    require_gpu(q, kv)
+    B, W = q.shape[0], nh * 64
+    ldq, ldk = _gen_rows("gen_attn_cross", q, "q"), _gen_rows("gen_attn_cross", kv, "kv")
+    if q.shape[1] != W or kv.shape[0] != B * n_keys or kv.shape[1] != 2 * W or kv.dtype != q.dtype:
+        raise KvqError(f"kvq.nnops.gen_attn_cross: q [B, {W}] needs kv [B * n_keys, {2 * W}] of its dtype, got {tuple(kv.shape)}")
+    if out is None:
+        out = torch.empty((B, W), dtype=q.dtype, device=q.device)
+    check(lib().kvq_gen_attn(_gen_ptr(state), q.data_ptr(), ldq, None, None, 0, kv.data_ptr(), ldk, int(n_keys) * ldk, B, nh, 0, int(n_keys), 0,
+                             io_dtype_of(q), out.data_ptr(), _gen_rows("gen_attn_cross", out, "out"), stream_ptr()), "kvq_gen_attn")
+    return out
+
+
+def gen_select(state, logits, V, ids, finished, lengths, step_logits=None):
+    """The next token of every sentence: ids[b, t + 1] = first arg-max over v < V of logits[b, v] (the state's temperature 0) or a
+    draw from softmax(logits / temperature) by the Gumbel-max trick (Philox keyed by the state's seed, t, b, v); prompt tokens are
+    kept, a finished sentence gets the pad id, the end token finishes one (include/kvq.h).  Temperature and seed live in the
+    state (new_gen_state), as t does.  step_logits [B, Lmax, V] f32: row (b, t) = the logits."""
+    require_gpu(logits, ids, finished, lengths)
+    B = logits.shape[0]
+    ld = _gen_rows("gen_select", logits, "logits")
+    if ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_contiguous() or ids.shape[0] != B:
+        raise KvqError("kvq.nnops.gen_select: ids must be a contiguous int64 [B, Lmax] tensor")
+    for name, x in (("finished", finished), ("lengths", lengths)):
+        if x.dtype != torch.int32 or x.shape != (B,) or not x.is_contiguous():
+            raise KvqError(f"kvq.nnops.gen_select: {name} must be a contiguous int32 [B] tensor")
+    if step_logits is not None and (step_logits.dtype != torch.float32 or tuple(step_logits.shape) != (B, ids.shape[1], V)
+                                    or not step_logits.is_contiguous()):
+        raise KvqError(f"kvq.nnops.gen_select: step_logits must be a contiguous float32 [B, Lmax, V] = {(B, ids.shape[1], V)} tensor")
+    check(lib().kvq_gen_select(_gen_ptr(state), logits.data_ptr(), ld, int(V), B, io_dtype_of(logits), ids.data_ptr(), finished.data_ptr(),
+                               lengths.data_ptr(), _p(step_logits), stream_ptr()), "kvq_gen_select")
+
+
+def gen_gumbel_debug(bits):
+    """g [n] f32 = the Gumbel(0, 1) value kvq_gen_select forms from each of the 32-bit patterns bits [n] (int64 holding 0 .. 2^32 - 1,
+    or int32 holding the bits): a test hook."""
+    require_gpu(bits)
+    if bits.dtype == torch.int64:
+        bits = (bits & 0xFFFFFFFF).to(torch.int32)      # (the low 32 bits, two's complement)
+    if bits.dtype != torch.int32 or bits.dim() != 1 or not bits.is_contiguous() or bits.numel() < 1:
+        raise KvqError("kvq.nnops.gen_gumbel_debug: a contiguous 1-D int32 / int64 tensor of bit patterns required")
+    out = torch.empty(bits.numel(), dtype=torch.float32, device=bits.device)
+    check(lib().kvq_gen_gumbel_debug(bits.data_ptr(), bits.numel(), out.data_ptr(), stream_ptr()), "kvq_gen_gumbel_debug")
+    return out
+
+
+def gen_advance(state):
+    """t += 1, on the device."""
+    check(lib().kvq_gen_advance(_gen_ptr(state), stream_ptr()), "kvq_gen_advance")
+
+
 # ---- EMA of the trained weights (include/kvq.h "exponential moving average of the trained weights") -------------------------------
 def new_weight_ema_state(device):
     """16 zeroed bytes: struct { uint64 updates; float last_decay; uint32 pad; } of include/kvq.h."""

@@ -156,6 +156,16 @@ class Bagon(nn.Module):
         return engine_of(self).decode(latents, decoder_input_ids, decoder_attention_mask, target_ids=target_ids, quantize=quantize,
                                       want_logits=want_logits)
 
+    def generate_from_latents(self, latents, max_length, prompt_ids, **kw):
+        """TrainEngine.generate: free-running generation from latents [B, Se, H] -- the decoder sees the prompt [B, P] (e.g. a column
+        of start ids) and what it has written itself, one token per position over a key/value cache: dict(ids [B, max_length],
+        lengths, finished [, logits] [, indices]).  kw: eos_id, pad_id, temperature, seed, quantize, want_logits, graph.  Meaningful
+        for a model trained with DECODER_NEXT_TOKEN."""
+        from kvq.engine import engine_of
+        return engine_of(self).generate(latents, max_length, prompt_ids, **kw)
+
+    decoder_next_token_start_id = None     # DECODER_NEXT_TOKEN: main.py puts the start id here, the trainer's step shifts the decoder input by it
+
     loss_ignore_index = None     # LOSS_IGNORE_PAD on the autograd path: main.py puts the pad id here, the trainer's step hands it to forward_loss
 
     def forward_loss(self, encoder_input_ids, encoder_attention_mask, decoder_input_ids, decoder_attention_mask, ignore_index=None):

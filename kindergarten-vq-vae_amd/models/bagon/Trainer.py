@@ -67,6 +67,13 @@ def step(device, model, tokenizer_encoder, tokenizer_decoder,
     if engine is not None:
         # the decoder side is handed over only when it differs from the encoder's: the autoencoding step then shares one sort
         dec = {} if input_ids_decoder is input_ids_encoder else dict(dec_ids=input_ids_decoder, dec_mask=attention_mask_decoder)
+        start_id = getattr(model, "decoder_next_token_start_id", None)
+        if start_id is not None:
+            # DECODER_NEXT_TOKEN: the decoder reads [start, ids[:-1]] and its logits at t are scored against ids[t], which it has
+            # not seen (the reference scores them against the token it has just been given); nothing else in the step changes
+            from kvq.functional import shift_right
+            dec = dict(dec_ids=shift_right(input_ids_decoder, int(start_id)), dec_mask=shift_right(attention_mask_decoder, 1),
+                       target_ids=input_ids_decoder)
         if opt is not None:
             packed = batch.get("packed") if isinstance(batch, dict) and not dec and encoder_perturb_pct == 0 else None
             out = engine.train_step(input_ids_encoder, attention_mask_encoder, prepared=packed, **dec)
@@ -74,6 +81,8 @@ def step(device, model, tokenizer_encoder, tokenizer_decoder,
             out = engine.eval_step(input_ids_encoder, attention_mask_encoder, **dec)
         loss_recon_step, acc_batch, acc_sentence, recon_ids = out["loss_recon"], out["acc"], out["acc_per_sentence"], out["recon_ids"]
     else:
+        if getattr(model, "decoder_next_token_start_id", None) is not None:
+            raise ValueError("DECODER_NEXT_TOKEN needs the engine step (it scores the logits against target_ids of its own)")
         pad = getattr(model, "loss_ignore_index", None)                                           # LOSS_IGNORE_PAD: the pad id
         loss_recon_step, acc_batch, recon_ids = model.forward_loss(input_ids_encoder, attention_mask_encoder,
                                                                    input_ids_decoder, attention_mask_decoder, ignore_index=pad)

@@ -108,6 +108,12 @@ def main():
         grad_sync = ddp.GradSync(model.parameters(), bucket_mib=GRAD_BUCKET_MIB)
     if engine is None and GRAD_ACCUM_STEPS > 1:      # the autograd path steps its optimiser per batch: no silent batch of another size
         raise SystemExit("GRAD_ACCUM_STEPS > 1 (KVQ_GRAD_ACCUM) needs the engine (USE_ENGINE and a model shape it supports)")
+    if DECODER_NEXT_TOKEN:      # next-token training: the trainer's step shifts the decoder input by this start id
+        if engine is None:
+            raise SystemExit("DECODER_NEXT_TOKEN needs the engine (USE_ENGINE and a model shape it supports)")
+        from kvq.tokenizer import CLS
+        start_id = getattr(tok_dec, "cls_token_id", None)
+        model.decoder_next_token_start_id = int(CLS if start_id is None else start_id)
     if engine is None and LOSS_IGNORE_PAD:      # the autograd path: forward_loss hands the pad id to fused_cross_entropy(ignore_index=...)
         model.loss_ignore_index = model.decoder.bert.embeddings.word_embeddings.padding_idx
         if model.loss_ignore_index is None:

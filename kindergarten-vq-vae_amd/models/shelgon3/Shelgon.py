@@ -90,13 +90,21 @@ class Shelgon(Bagon):
         return engine_of(self).decode_codes(indices, decoder_input_ids, decoder_attention_mask, target_ids=target_ids,
                                             want_logits=want_logits)
 
+    def generate_from_codes(self, indices, max_length, prompt_ids, **kw):
+        """TrainEngine.generate_codes: the sentence a code sequence produces -- free-running generation (Bagon.generate_from_latents)
+        from the codebook rows of indices [B, Se] / [B, Se, G]."""
+        from kvq.engine import engine_of
+        return engine_of(self).generate_codes(indices, max_length, prompt_ids, **kw)
+
     def traverse_codes(self, input_ids, attention_mask, sentence, position, decoder_input_ids=None, decoder_attention_mask=None,
-                       factor=0):
+                       factor=0, free_running=False, max_length=None, start_id=None):
         """TrainEngine.traverse_codes: the reconstructions of one sentence under every code at (position, factor):
-        dict(recon_ids [K, Sd], own_code, changed [K, Sd])."""
+        dict(recon_ids [K, Sd], own_code, changed [K, Sd]).  free_running=True: the K variants are generated from start_id (default:
+        the sentence's first decoder id) instead of decoded against the sentence's own ids."""
         from kvq.engine import engine_of
         return engine_of(self).traverse_codes(input_ids, attention_mask, sentence, position, dec_ids=decoder_input_ids,
-                                              dec_mask=decoder_attention_mask, factor=factor)
+                                              dec_mask=decoder_attention_mask, factor=factor, free_running=free_running,
+                                              max_length=max_length, start_id=start_id)
 
     def forward_loss(self, input_ids, attention_mask, ignore_index=None):
         """Fused step body: (vq_loss, perplexity, indices, loss_recon, acc_per_batch, recon_ids)."""

@@ -50,8 +50,16 @@ def step(device, model, tokenizer, tokenizer_add_special_tokens: bool, opt,
     if engine is not None:
         # fast path: kvq.engine.TrainEngine runs forward, backward, gradient exchange and Adam (+ the per-step scheduler
         # tick) itself; the loss weights were given to its constructor
-        out = engine.train_step(input_ids, attention_mask, prepared=batch.get("packed") if isinstance(batch, dict) else None) \
-            if opt is not None else engine.eval_step(input_ids, attention_mask)
+        start_id = getattr(model, "decoder_next_token_start_id", None)
+        if start_id is not None:
+            # DECODER_NEXT_TOKEN: the decoder reads [start, ids[:-1]] and its logits at t are scored against ids[t], which it has
+            # not seen (the reference scores them against the token it has just been given); nothing else in the step changes
+            from kvq.functional import shift_right
+            dec = dict(dec_ids=shift_right(input_ids, int(start_id)), dec_mask=shift_right(attention_mask, 1), target_ids=input_ids)
+            out = engine.train_step(input_ids, attention_mask, **dec) if opt is not None else engine.eval_step(input_ids, attention_mask, **dec)
+        else:
+            out = engine.train_step(input_ids, attention_mask, prepared=batch.get("packed") if isinstance(batch, dict) else None) \
+                if opt is not None else engine.eval_step(input_ids, attention_mask)
         stats = {
             "loss_recon_step": out["loss_recon"].detach(), "loss_vq_step": out["loss_vq"].detach(),
             "metric_perp_step": out["perplexity"].detach(), "loss_full_step": (out["loss_recon"] + out["loss_vq"]).detach(),
@@ -69,6 +77,8 @@ def step(device, model, tokenizer, tokenizer_add_special_tokens: bool, opt,
             stats["lr_step"] = out["lr"]
         return stats, input_ids, out["recon_ids"]
 
+    if getattr(model, "decoder_next_token_start_id", None) is not None:
+        raise ValueError("DECODER_NEXT_TOKEN needs the engine step (it scores the logits against target_ids of its own)")
     loss_vq_step, metric_perp_step, _indices, loss_recon_step, acc_step, recon_ids = \
         model.forward_loss(input_ids, attention_mask, ignore_index=getattr(model, "loss_ignore_index", None))      # LOSS_IGNORE_PAD: the pad id
 

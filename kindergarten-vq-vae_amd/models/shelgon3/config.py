@@ -40,6 +40,7 @@ GRAD_ACCUM_STEPS = 1                 # int >= 1: train_step calls (micro-batches
 WEIGHT_EMA_DECAY = None            # None (off) | float in (0, 1): the engine keeps an f32 moving average of the trained weights, updated behind Adam inside the step (the decay warms up as min(decay, (1 + t) / (10 + t))); KVQ_WEIGHT_EMA; DESIGN.md section 5f
 WEIGHT_EMA_EVAL = True              # with WEIGHT_EMA_DECAY: validation, the best-val checkpoints and the test stage run under the average (False: the average is kept and saved with the training state, evaluation reads the live weights)
 LOSS_IGNORE_PAD = False             # False | True: the engine step takes the reconstruction loss, the accuracy and the per-sentence accuracy over the tokens whose target is not the pad id (F.cross_entropy's ignore_index) instead of over all B*S positions; KVQ_LOSS_IGNORE_PAD; DESIGN.md section 5g
+DECODER_NEXT_TOKEN = False          # False | True: next-token training -- the decoder reads shift_right(ids, [CLS]) and its logits at t are scored against ids[t] (target_ids), instead of the reference's unshifted loss, under which a causal decoder is scored against the token it has just been given and learns to copy it; needs the engine; free-running generation (TrainEngine.generate) is meaningful only for a model trained this way; DESIGN.md section 5i
 PARAM_GROUPS = None                 # None (off) | list of {"match": pattern | [patterns], "lr_scale": float >= 0 (1), "weight_decay": float >= 0 (WEIGHT_DECAY)}: fnmatch patterns over the engine's parameter names (engine.param_names()), first match wins, the rest trains under LR and WEIGHT_DECAY; e.g. [{"match": ["*.b", "*.ln.w", "*.ln2.w", "head.bias"], "weight_decay": 0.0}] (= kvq.engine.NO_DECAY); KVQ_PARAM_GROUPS (JSON); DESIGN.md section 5h
 DECOUPLED_WEIGHT_DECAY = False      # False | True: torch.optim.AdamW's decoupled decay instead of Adam's coupled L2 term, in the engine's Adam kernel; KVQ_DECOUPLED_WD (0 / 1)
 LR_WARMUP_STEPS = 0                 # int >= 0: the rate climbs as t / LR_WARMUP_STEPS over the first optimiser steps (0: off); multiplies the MultiStepLR factor
@@ -136,6 +137,10 @@ if LOSS_IGNORE_PAD in (0, 1) and not isinstance(LOSS_IGNORE_PAD, bool) and _os.e
     LOSS_IGNORE_PAD = bool(LOSS_IGNORE_PAD)      # the environment spells the switch 0 / 1, as TrainEngine reads it
 if not isinstance(LOSS_IGNORE_PAD, bool):
     raise ValueError(f"LOSS_IGNORE_PAD (KVQ_LOSS_IGNORE_PAD) must be True or False (0 or 1 in the environment), got {LOSS_IGNORE_PAD!r}")
+if DECODER_NEXT_TOKEN in (0, 1) and not isinstance(DECODER_NEXT_TOKEN, bool) and _os.environ.get("KVQ_DECODER_NEXT_TOKEN", "").strip() in ("0", "1"):
+    DECODER_NEXT_TOKEN = bool(DECODER_NEXT_TOKEN)      # the environment may spell the switch 0 / 1, as KVQ_LOSS_IGNORE_PAD
+if not isinstance(DECODER_NEXT_TOKEN, bool):
+    raise ValueError(f"DECODER_NEXT_TOKEN (KVQ_DECODER_NEXT_TOKEN) must be True or False (0 or 1 in the environment), got {DECODER_NEXT_TOKEN!r}")
 _v = _os.environ.get("KVQ_DECOUPLED_WD", "").strip()      # the variable TrainEngine itself reads; it wins over KVQ_DECOUPLED_WEIGHT_DECAY; empty = unset
 if _v:
     DECOUPLED_WEIGHT_DECAY = {"0": False, "1": True}.get(_v, _v)

@@ -1,0 +1,118 @@
+"""Rate of TrainEngine.generate and where a generation step's time goes, on ONE engine in ONE process:
+bert-base-uncased encoder / decoder (random weights: the rate does not depend on them), bf16, B sentences, Se latent rows,
+max_length positions, greedy, no end token.  Three arms, alternated round by round after one warm-up call each (the warm-up of
+the first arm includes the capture of the step):
+
+  graph          generate(graph=True): the captured step replayed max_length - 1 times
+  eager          generate(graph=False): the same launches issued one by one
+  prefix_decode  what the engine offered before generate(): decode() once per position on the growing prefix, the next token
+                 taken from recon_ids[:, -1] and appended on the device (no host read either)
+
+Every call is timed twice: by device events recorded around it on the current stream, and by the host clock around the call and
+a device synchronise.  Then: about `--replays` back-to-back replays of the captured step alone (whole passes over the positions)
+between two events (ms per step), the node census of the captured step, a sampling arm (graph, temperature 1, a new seed per call: the same captured step), and one
+eager call under kvq._ffi.family_profile_begin() -- an event pair around every entry point, the empty pair subtracted -- for
+the split of a step between the GEMMs, kvq_gen_attn and the rest.
+Prints one JSON document; profiles/generate.md records it.
+
+    PYTHONPATH=kindergarten-vq-vae_amd python3 tools/generate_timing.py [--out FILE.json] [--rounds 5] [--batch 256] [--se 32] [--max-length 32]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "kindergarten-vq-vae_amd")]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--se", type=int, default=32)
+    ap.add_argument("--max-length", type=int, default=32)
+    ap.add_argument("--replays", type=int, default=310)
+    ap.add_argument("--model", default="bert-base-uncased")
+    a = ap.parse_args()
+    import torch
+
+    from kvq import _ffi
+    from kvq.engine import engine_of
+    from models.bagon.Bagon import Bagon
+    if not torch.cuda.is_available():
+        raise SystemExit("generate_timing.py measures on the GPU: there is no CPU path and no number without one")
+    B, SE, L = a.batch, a.se, a.max_length
+    torch.manual_seed(0)
+    model = Bagon(a.model, a.model, True, compute_dtype=torch.bfloat16).cuda().eval()
+    eng = engine_of(model)
+    lat = torch.randn((B, SE, eng.H), generator=torch.Generator().manual_seed(1)).to(torch.bfloat16).cuda().contiguous()
+    prompt = torch.full((B, 1), 101, dtype=torch.int64, device="cuda")
+    tokens = B * (L - 1)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return dict(host_s=time.perf_counter() - t0, event_s=e0.elapsed_time(e1) * 1e-3), out
+
+    def prefix_loop():
+        ids = prompt
+        for _ in range(L - 1):
+            nxt = eng.decode(lat, ids, torch.ones_like(ids))["recon_ids"][:, -1:]
+            ids = torch.cat([ids, nxt], 1)
+        return ids
+
+    seeds = iter(range(1, 1 << 30))
+    arms = {"graph": lambda: eng.generate(lat, L, prompt)["ids"],
+            "eager": lambda: eng.generate(lat, L, prompt, graph=False)["ids"],
+            "prefix_decode": prefix_loop,
+            "graph_sampling_new_seed_per_call": lambda: eng.generate(lat, L, prompt, temperature=1.0, seed=next(seeds))["ids"]}
+    res = {"model": a.model, "B": B, "Se": SE, "max_length": L, "tokens_per_call": tokens, "rounds": a.rounds,
+           "device": torch.cuda.get_device_name(0)}
+    with torch.no_grad():
+        first = {k: fn() for k, fn in arms.items()}                       # warm-up of every arm (capture included)
+        res["graph_equals_eager"] = bool(torch.equal(first["graph"], first["eager"]))
+        res["prefix_loop_tokens_differing_from_generate"] = int((first["prefix_decode"] != first["graph"]).sum())
+        times = {k: [] for k in arms}
+        for _ in range(a.rounds):                                          # alternating rounds
+            for k, fn in arms.items():
+                times[k].append(timed(fn)[0])
+        for k, v in times.items():
+            ev, ho = sorted(t["event_s"] for t in v), sorted(t["host_s"] for t in v)
+            res[k] = dict(event_s_median=ev[len(ev) // 2], event_s_min=ev[0], event_s_max=ev[-1], host_s_median=ho[len(ho) // 2],
+                          host_s_min=ho[0], host_s_max=ho[-1], tokens_per_s_median=tokens / ev[len(ev) // 2])
+        res["captured_steps_kept"] = len(eng._gen_cache)                   # one: sampling under new seeds reuses the greedy call's graph
+        entry = next(iter(eng._gen_cache.values()))
+        eng.generate(lat, L, prompt)                                       # leaves a valid state, prompt and latent projection behind
+
+        def replay_block():                                                # whole passes over the positions: t back to 0 (one fill
+            for _ in range(max(a.replays // (L - 1), 1)):                  # kernel per pass), then the L - 1 steps -- a step past the
+                entry["state"][0:1].zero_()                                # last position would find t outside its buffers and skip
+                for _ in range(L - 1):                                     # the attention and selection work
+                    entry["graph"].replay()
+        dt, _ = timed(replay_block)
+        res["graph_replay_ms_per_step"] = 1e3 * dt["event_s"] / (max(a.replays // (L - 1), 1) * (L - 1))
+        res["census"] = eng.gen_census()
+        _ffi.family_profile_begin()
+        eng.generate(lat, L, prompt, graph=False)
+        ms, n, empty = _ffi.family_profile_end()
+        res["eager_family_ms_per_call"] = ms
+        res["eager_family_launches_per_call"] = n
+        res["empty_event_pair_ms"] = empty
+    text = json.dumps(res, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
