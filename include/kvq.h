@@ -498,10 +498,15 @@ int kvq_gemm_fp8_nt_gelu(const void* A8, const void* B8, const float* scale_a, c
  *   kernel of kvq_gemm_fp8_nt (same bits). */
 int kvq_gemm_fp8_nt_ex(const void* A8, const void* B8, const float* scale_a, const float* scale_b, const void* bias, void* C,
                        int M, int N, int K, int lda, int ldb, int ldc, int a_format, int accumulate, void* stream);
+/* The tile kvq_gemm_fp8_nt / kvq_gemm_fp8_nt_ex launch for an [M, N] output on the current device: KVQ_GEMM_TILE_128x256, or
+ *   KVQ_GEMM_TILE_128x192 where that fills more CUs (the same function decides for the launch).  -1 for M or N <= 0.  No launch. */
+int kvq_gemm_fp8_tile(int M, int N);
 /* The quantisation calls above with the target format as an argument (fmt = KVQ_FP8_E4M3: the bytes of the calls above);
  * round to nearest even, saturating at the format's largest value, a NaN stays a NaN.  Rows may be strided (ld >= cols, cols and
  * ld %% 8 == 0); rows of a multiple of 16 columns are written in 16-byte pieces.  Kernel launches only: all three can be captured.
- *   kvq_fp8_quantize_fmt         : amax pass + quantise pass, scale = max(fmt) / amax of the tensor itself (amax, scale: written)
+ *   kvq_fp8_quantize_fmt         : amax pass + quantise pass, scale = max(fmt) / amax of the tensor itself (amax, scale: written).
+ *                                  An inf in the tensor does NOT saturate here (nor in kvq_fp8_quantize): amax = inf, scale = 0,
+ *                                  every finite value becomes a signed zero and the inf itself 0 * inf = NaN
  *   kvq_fp8_quantize_delayed_fmt : one pass with the record's scale, this tensor's amax left in the record's partials (the record
  *                                  layout of kvq_fp8_quantize_delayed).  out_fp8 == NULL: only the amax is noted (calibration)
  *   kvq_fp8_update_scales_fmt    : scale = max(fmt) / (amax * headroom) for nsites consecutive records of ONE format; a record

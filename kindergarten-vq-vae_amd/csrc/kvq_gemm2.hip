@@ -1348,6 +1348,16 @@ static int build_params(const kvq_gemm_problem* probs, int nprob, int layout, in
     return KVQ_OK;
 }
 
+// Tile of the fp8 NT GEMMs (round 5): 128 x 256 unless that leaves CUs without a tile and 128 x 192 does not -- an [8192, 768] output is
+// 192 tiles of the first and 256 of the second (KVQ_FP8_TILE=0: always 128 x 256, the rounds 2 - 4 behaviour; A/B switch).  The one
+// place that decides: gemm_fp8_nt_impl launches what this returns, kvq_gemm_fp8_tile reports it.
+static int fp8_tile_of(int M, int N) {
+    static const bool narrow_ok = !(getenv("KVQ_FP8_TILE") && atoi(getenv("KVQ_FP8_TILE")) == 0);
+    const int t256 = ((M + 127) / 128) * ((N + 255) / 256), t192 = ((M + 127) / 128) * ((N + 191) / 192);
+    const bool narrow = narrow_ok && t256 < g2::persistent_grid() && t192 > t256;
+    return narrow ? KVQ_GEMM_TILE_128x192 : KVQ_GEMM_TILE_128x256;
+}
+
 // AFMT = KVQ_FP8_E4M3, accumulate = 0: kvq_gemm_fp8_nt.  accumulate: the EPI_NONE epilogue's C += (the bf16 kernel's), unchanged.
 template <int AFMT>
 static int gemm_fp8_nt_impl(const void* A8, const void* B8, const float* scale_a, const float* scale_b, const void* bias, void* C, int M, int N,
@@ -1358,11 +1368,7 @@ static int gemm_fp8_nt_impl(const void* A8, const void* B8, const float* scale_a
     q.A = A8; q.B = B8; q.C = C; q.bias = bias; q.M = M; q.N = N; q.K = K / 2; q.lda = lda / 2; q.ldb = ldb / 2; q.ldc = ldc;
     q.accumulate = accumulate != 0;
     g2::Params P;
-    // Tile (round 5): 128 x 256 unless that leaves CUs without a tile and 128 x 192 does not -- an [8192, 768] output is 192 tiles of
-    // the first and 256 of the second (KVQ_FP8_TILE=0: always 128 x 256, the rounds 2 - 4 behaviour; A/B switch)
-    static const bool narrow_ok = !(getenv("KVQ_FP8_TILE") && atoi(getenv("KVQ_FP8_TILE")) == 0);
-    const int t256 = ((M + 127) / 128) * ((N + 255) / 256), t192 = ((M + 127) / 128) * ((N + 191) / 192);
-    const bool narrow = narrow_ok && t256 < g2::persistent_grid() && t192 > t256;
+    const bool narrow = fp8_tile_of(M, N) == KVQ_GEMM_TILE_128x192;
     if (int rc = build_params(&q, 1, KVQ_GEMM_NT, narrow ? KVQ_GEMM_TILE_128x192 : KVQ_GEMM_TILE_128x256, P, who)) return rc;
     for (int i = 0; i < g2::MAX_PROBLEMS; ++i) { P.p[i].scaleA = scale_a; P.p[i].scaleB = scale_b; }
     hipStream_t st = (hipStream_t)stream;
@@ -1540,6 +1546,8 @@ int kvq_gemm_fp8_nt_ex(const void* A8, const void* B8, const float* scale_a, con
         return gemm_fp8_nt_impl<KVQ_FP8_E5M2>(A8, B8, scale_a, scale_b, bias, C, M, N, K, lda, ldb, ldc, accumulate, stream, "kvq_gemm_fp8_nt_ex");
     return gemm_fp8_nt_impl<KVQ_FP8_E4M3>(A8, B8, scale_a, scale_b, bias, C, M, N, K, lda, ldb, ldc, accumulate, stream, "kvq_gemm_fp8_nt_ex");
 }
+
+int kvq_gemm_fp8_tile(int M, int N) { return M > 0 && N > 0 ? fp8_tile_of(M, N) : -1; }
 
 int kvq_gemm_fp8_nt_gelu(const void* A8, const void* B8, const float* scale_a, const float* scale_b, const void* bias, void* Hout, void* Aout,
                          void* Aout_fp8, int ld8, float* fp8_state, int M, int N, int K, int lda, int ldb, int ldc, void* stream) {

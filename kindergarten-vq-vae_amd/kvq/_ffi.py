@@ -112,6 +112,7 @@ SIGNATURES = {
     "kvq_fp8_quantize_segments_periodic": (_int, [_vp, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _int, _vp]),
     "kvq_gemm_fp8_nt": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _vp]),
     "kvq_gemm_fp8_nt_ex": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _int, _int, _int, _int, _vp]),
+    "kvq_gemm_fp8_tile": (_int, [_int, _int]),
     "kvq_fp8_quantize_fmt": (_int, [_vp, _i64, _int, _i64, _vp, _vp, _vp, _int, _vp]),
     "kvq_fp8_quantize_delayed_fmt": (_int, [_vp, _i64, _int, _i64, _vp, _vp, _int, _vp]),
     "kvq_fp8_update_scales_fmt": (_int, [_vp, _int, _f32, _int, _vp]),

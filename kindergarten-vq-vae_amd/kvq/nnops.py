@@ -1190,6 +1190,14 @@ def gemm_fp8_nt(a8, b8, scale_a, scale_b, bias=None, out=None, a_format=None, ac
     return out
 
 
+def gemm_fp8_tile(M, N):
+    """The name of the tile ("128x256" / "128x192") gemm_fp8_nt launches for an [M, N] output (kvq_gemm_fp8_tile: the launch's own rule)."""
+    t = lib().kvq_gemm_fp8_tile(int(M), int(N))
+    if t not in TILE_NAMES:
+        raise KvqError(f"kvq_gemm_fp8_tile({M}, {N}) returned {t}")
+    return TILE_NAMES[t]
+
+
 def gemm_fp8_nt_gelu(a8, b8, scale_a, scale_b, bias, state_out=None):
     """(h, gelu(h)[, fp8 copy of gelu(h)]) with h = (a8 @ b8.T) / (scale_a * scale_b) + bias on the fp8 matrix cores: BertIntermediate
     with the GELU epilogue of gemm_gelu; state_out = the delayed-scaling record of the fp8 GEMM that reads gelu(h) next."""

@@ -72,7 +72,8 @@ def _bytes(rows, cols, seed):
     return torch.randint(0, 256, (rows, cols), generator=g, device="cuda", dtype=torch.int32).to(torch.uint8)
 
 
-@pytest.mark.parametrize("rows,cols,ld", [(16, 16, 16), (128, 128, 128), (2304, 768, 768), (784, 272, 304)])
+@pytest.mark.parametrize("rows,cols,ld", [(16, 16, 16), (128, 128, 128), (2304, 768, 768), (784, 272, 304),
+                                          (16, 2064, 2064), (2064, 16, 16)])     # one tile row / column of 17 tiles, every one an edge tile
 def test_transpose_is_bitwise(rows, cols, ld):
     from kvq import nnops
     buf = _bytes(rows, ld, rows + cols)
