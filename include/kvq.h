@@ -867,6 +867,51 @@ int kvq_gen_gumbel_debug(const uint32_t* bits, int64_t n, float* out, void* stre
 int kvq_gen_advance(void* state, void* stream);
 
 
+/* ---- beam search over the key/value cache (csrc/kvq_generate.hip) ------------------------------------------
+ * Slot space: beam w of sentence b is row r = b W + w of every [R, ...] buffer, R >= B W (the engine rounds it up to 8; a last
+ * sentence with fewer than W rows is handled).  Nothing is ever moved: row (r, t) of a cache and ids[r, t] are written once, by
+ * row r at position t, and a beam's HISTORY is a row of the ancestry table
+ *     anc [2, R, Lmax] int32, ping-ponged on the parity of t:  anc[t & 1][r, j], j <= t  =  the slot whose cache row j and token j
+ *     belong to the history of the beam now living in row r          (both halves start as the identity, anc[., r, j] = r)
+ * beside ids [R, Lmax] int64 (slot tokens: kvq_gen_embed and kvq_gen_advance run on it unchanged), parent [R, Lmax] int32,
+ * step_scores [R, Lmax] f32, scores [R] f32 (sums of log-probabilities; -inf = a dead beam, which offers nothing), finished [R],
+ * lengths [R] int32.  The state is the generation state above with inv_tau = 0, seed = 0; every kernel reads t from it.  Kernels
+ * only, no atomics, fixed summation orders: the same inputs give the same bits.  f32 and bf16 io.
+ *
+ * kvq_beam_attn    kvq_gen_attn with two indirections in the addresses; arithmetic, lane mapping and summation order are that
+ *                  kernel's (one body): on a cache gathered physically by the same ancestry the two agree bit for bit.
+ *                    append != 0: row r stores its k_new | v_new to cache row (r, t) and attends over keys j = 0 .. t, key j < t read
+ *                      from cache row (anc[t & 1][r, j], j), key t from k_new / v_new themselves (no workgroup waits for another's
+ *                      store).  anc_ld = Lmax >= Smax.  A slot outside [0, R) reads row r.
+ *                    append == 0: row r reads the n_keys rows of sentence r / rows_per_sentence of kv.
+ * kvq_beam_select  one step of the search, one workgroup a sentence (rows b W .. b W + W - 1, W = 1 .. 8, W <= V); everything of
+ *                  the old state is read before anything is written.  Stores nothing unless 0 <= t and t + 1 < Lmax.
+ *                    t + 1 < P (prompt): ids kept, parent[r, t+1] = r, step_scores[r, t+1] = scores[r], the history extended by
+ *                      anc'[r, 0 .. t] = anc[r, 0 .. t], anc'[r, t+1] = r      (anc = half t & 1, anc' = half (t + 1) & 1).
+ *                    otherwise the candidates are: of a live beam w (not finished, score > -inf) every v < V with
+ *                        lp = fl(x[w, v] - lse_w),  s = fl(score_w + lp),  lse_w = m + log sum_v exp(x[w, v] - m)   (f32)
+ *                      -- a beam with a NaN among its columns < V offers nothing, a candidate with s = -inf or NaN is none --;
+ *                      of a finished beam exactly one: token pad_id, s = score_w, ranking in ties as (w, 0).  New beam i = the i-th
+ *                      best: larger s, then lower w, then lower v.  For the new row r' = b W + i with parent w:
+ *                        ids[r', t+1] = v, parent[r', t+1] = b W + w, scores[r'] = step_scores[r', t+1] = s, finished / lengths of w,
+ *                        v == eos_id: finished = 1, lengths = t + 2;  anc'[r', 0 .. t] = anc[b W + w, 0 .. t], anc'[r', t+1] = r'.
+ *                      Fewer than W candidates: the rest become dead beams (score -inf, token pad_id, parent = self, finished = 1,
+ *                      their own history).
+ *                    The logits are read once, 16 bytes a lane; the chain of f32 roundings in front of lse_w is bounded by 256
+ *                    (refused otherwise: V up to 55 296 with 5 .. 8 beams, 106 496 with 3 or 4, more with fewer), which is what the tolerance of tests/_beam_ref.py rests on.
+ *                    step_logits (may be NULL) [R, Lmax, V] f32: row (r, t) receives the logits of every row in the prompt, of
+ *                    the live beams afterwards.  ld %% 8 == 0, 16-byte aligned logits.
+ * kvq_beam_gather  hypotheses from slot space: out[r, j] = ids[anc[t & 1][r, j], j] for j < lengths[r] (j <= t), pad_id behind. */
+int kvq_beam_attn(const void* state, const void* q, int64_t ldq, const void* k_new, const void* v_new, int64_t ld_new, void* kv,
+                  int64_t ld_kv, int64_t kv_sentence_stride, int R, int nh, int append, int n_keys, int Smax, const int32_t* anc,
+                  int anc_ld, int rows_per_sentence, int io_dtype, void* out, int64_t ldo, void* stream);
+int kvq_beam_select(const void* state, const void* logits, int64_t ld, int V, int R, int W, int Lmax, int io_dtype, int64_t* ids,
+                    int32_t* parent, float* scores, float* step_scores, int32_t* anc, int32_t* finished, int32_t* lengths,
+                    float* step_logits, void* stream);
+int kvq_beam_gather(const void* state, const int64_t* ids, const int32_t* anc, const int32_t* lengths, int R, int Lmax, int64_t* out,
+                    void* stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,7 @@ VQ_BETA = 0.1
 CKPT_PATH = None                     # "<RUN_DIR>/bagon_ckpt_loss_recon_val_best.pth" (:55); None = fresh weights
 RESULTS_DIR = None                   # default: <RUN_DIR>
 FREE_RUNNING = False                 # True (or --free-running on the command line): the plain and the edited latent are GENERATED from each sentence's first token (model.generate_from_latents) instead of decoded against the sentence's own ids; for a model trained with DECODER_NEXT_TOKEN
+NUM_BEAMS = 1                        # N > 1 (or --num-beams N on the command line; with free running): the plain and the edited sentence are the best of N hypotheses of beam search (model.generate_from_latents(num_beams=N)); the table gains recon_ / edited_ score, runner_up_<i> and runner_up_<i>_score columns
 
 for _k in [k for k in list(globals()) if k.isupper()]:
     _v = os.environ.get("KVQ_" + _k)
@@ -95,8 +96,24 @@ def _tokenize(tokenizer, sentences, device, seq_len, add_special_tokens):
     return t.input_ids.to(device, non_blocking=True), t.attention_mask.to(device, non_blocking=True)
 
 
+def beam_columns(tokenizer, beam_ids, beam_scores, prefix=""):
+    """score of the best hypothesis and the runner-ups of one sentence as table columns: beam_ids [W, L], beam_scores [W], best first"""
+    texts, scores = tokenizer.batch_decode(beam_ids.cpu()), beam_scores.cpu().tolist()
+    cols = {prefix + "score": scores[0]}
+    for i in range(1, len(texts)):
+        cols[f"{prefix}runner_up_{i}"] = texts[i]
+        cols[f"{prefix}runner_up_{i}_score"] = scores[i]
+    return cols
+
+
+def num_beams_switch(default):
+    """--num-beams N on the command line, else the configured constant"""
+    argv = sys.argv[1:]
+    return int(argv[argv.index("--num-beams") + 1]) if "--num-beams" in argv else int(default)
+
+
 def latent_arithmetics(model, tokenizer, s_neg, s_aff, s_edit, device, seq_len, batch_size, add_special_tokens=False, alpha=1.0,
-                       free_running=False):
+                       free_running=False, num_beams=1):
     """-> (LatentCensus over group 0 = s_aff, group 1 = s_neg; rows of original / reconstructed / edited sentences of s_edit)"""
     H = model.encoder.config.hidden_size
     quantize = hasattr(model, "vector_quantizer")
@@ -111,13 +128,19 @@ def latent_arithmetics(model, tokenizer, s_neg, s_aff, s_edit, device, seq_len, 
         z = model.encode_latents(ids, mask, quantize=False)["z"]
         if free_running:                        # what the latent says by itself: the decoder sees the first token and its own output
             start = ids[:, :1].contiguous()
-            plain = model.generate_from_latents(z, seq_len, start, quantize=quantize)["ids"]
-            edited = model.generate_from_latents(census.shift(z, 1, 0, alpha=alpha), seq_len, start, quantize=quantize)["ids"]
+            plain_out = model.generate_from_latents(z, seq_len, start, quantize=quantize, num_beams=num_beams)
+            edited_out = model.generate_from_latents(census.shift(z, 1, 0, alpha=alpha), seq_len, start, quantize=quantize, num_beams=num_beams)
+            plain, edited = plain_out["ids"], edited_out["ids"]
         else:
             plain = model.decode_latents(z, ids, mask, quantize=quantize)["recon_ids"]
             edited = model.decode_latents(census.shift(z, 1, 0, alpha=alpha), ids, mask, quantize=quantize)["recon_ids"]
+        first = len(rows)
         for s, r, e in zip(batch, tokenizer.batch_decode(plain.cpu()), tokenizer.batch_decode(edited.cpu())):
             rows.append({"input_sentence": s, "recon_sentence": r, "edited_sentence": e})
+            if free_running and num_beams > 1:  # the runner-up hypotheses and the sums of log-probabilities
+                i = len(rows) - 1 - first
+                rows[-1].update(beam_columns(tokenizer, plain_out["beam_ids"][i], plain_out["beam_scores"][i], "recon_"))
+                rows[-1].update(beam_columns(tokenizer, edited_out["beam_ids"][i], edited_out["beam_scores"][i], "edited_"))
     return census, rows
 
 
@@ -156,7 +179,8 @@ def main():
     torch.set_grad_enabled(False)                                                            # :45
     tokenizer = load_tokenizer(TOKENIZER_NAME)
     census, rows = latent_arithmetics(model, tokenizer, s_neg, s_aff, s_edit, device, TOKENIZED_SENTENCE_MAX_LENGTH, BATCH_SIZE,
-                                      TOKENIZER_ADD_SPECIAL_TOKENS, ALPHA, free_running=bool(FREE_RUNNING) or "--free-running" in sys.argv[1:])
+                                      TOKENIZER_ADD_SPECIAL_TOKENS, ALPHA, free_running=bool(FREE_RUNNING) or "--free-running" in sys.argv[1:],
+                                      num_beams=num_beams_switch(NUM_BEAMS))
     results_dir = RESULTS_DIR or run_dir
     os.makedirs(results_dir, exist_ok=True)
     written = write_table(pd.DataFrame(rows), f"{results_dir}/latent_arithmetics.feather")

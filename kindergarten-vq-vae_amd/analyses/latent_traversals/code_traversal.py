@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))      # package root 
 import torch  # noqa: E402
 
 from analyses.get_max_acc_sentences import read_table, write_table  # noqa: E402
-from analyses.latent_arithmetics.latent_arithmetics import corpus_table  # noqa: E402
+from analyses.latent_arithmetics.latent_arithmetics import beam_columns, corpus_table, num_beams_switch  # noqa: E402
 from common.consts import *  # noqa: E402,F401,F403
 from kvq.tokenizer import load_tokenizer  # noqa: E402
 from models.shelgon3.MultiVectorQuantizer import MultiVectorQuantizer  # noqa: E402
@@ -59,6 +59,7 @@ VQ_N_FACTORS = 1
 CKPT_PATH = None                     # "<RUN_DIR>/Shelgon_ckpt_loss_recon_val_best.pth" (:55); None = fresh weights
 RESULTS_DIR = None                   # default: <RUN_DIR>
 FREE_RUNNING = False                 # True (or --free-running on the command line): the K variants are GENERATED from the sentence's first token (model.traverse_codes(free_running=True)) instead of decoded against the sentence's own ids; for a model trained with DECODER_NEXT_TOKEN
+NUM_BEAMS = 1                        # N > 1 (or --num-beams N on the command line; with free running): every variant is the best of N hypotheses of beam search (model.traverse_codes(num_beams=N)); the table gains score, runner_up_<i> and runner_up_<i>_score columns
 
 for _k in [k for k in list(globals()) if k.isupper()]:
     _v = os.environ.get("KVQ_" + _k)
@@ -69,20 +70,24 @@ for _k in [k for k in list(globals()) if k.isupper()]:
             globals()[_k] = _v
 
 
-def code_traversal(model, tokenizer, sentences, device, seq_len, positions=None, factor=0, add_special_tokens=False, free_running=False):
-    """Rows of the result table for every (sentence, position, code).  free_running: the variants are generated, not teacher-forced."""
+def code_traversal(model, tokenizer, sentences, device, seq_len, positions=None, factor=0, add_special_tokens=False, free_running=False,
+                   num_beams=1):
+    """Rows of the result table for every (sentence, position, code).  free_running: the variants are generated, not teacher-forced;
+    num_beams > 1: by beam search, the runner-up hypotheses and the scores (sums of log-probabilities) in columns of their own."""
     t = tokenizer(list(sentences), return_tensors="pt", padding="max_length", max_length=seq_len, add_special_tokens=add_special_tokens)
     ids, mask = t.input_ids.to(device), t.attention_mask.to(device)                          # :98-108
     lengths = t.attention_mask.sum(1).tolist()
     rows = []
     for b, sentence in enumerate(sentences):
         for pos in (positions if positions is not None else range(int(lengths[b]))):
-            out = model.traverse_codes(ids, mask, b, int(pos), factor=factor, free_running=free_running)      # :139-150
+            out = model.traverse_codes(ids, mask, b, int(pos), factor=factor, free_running=free_running, num_beams=num_beams)   # :139-150
             decoded = tokenizer.batch_decode(out["recon_ids"].cpu())                         # :158-160
             n_changed = out["changed"].sum(1).tolist()
             for k, (r, c) in enumerate(zip(decoded, n_changed)):
                 rows.append({"input_sentence": sentence, "position": int(pos), "code": k, "own_code": k == out["own_code"],
                              "recon_sentence": r, "n_changed_tokens": int(c)})
+                if "beam_ids" in out:
+                    rows[-1].update(beam_columns(tokenizer, out["beam_ids"][k], out["beam_scores"][k]))
     return rows
 
 
@@ -117,7 +122,8 @@ def main():
     torch.set_grad_enabled(False)                                                            # :42
     tokenizer = load_tokenizer(TOKENIZER_NAME)
     rows = code_traversal(model, tokenizer, all_gen_fact, device, TOKENIZED_SENTENCE_MAX_LENGTH, POSITIONS, FACTOR_INDEX,
-                          TOKENIZER_ADD_SPECIAL_TOKENS, free_running=bool(FREE_RUNNING) or "--free-running" in sys.argv[1:])
+                          TOKENIZER_ADD_SPECIAL_TOKENS, free_running=bool(FREE_RUNNING) or "--free-running" in sys.argv[1:],
+                          num_beams=num_beams_switch(NUM_BEAMS))
     results_dir = RESULTS_DIR or run_dir
     os.makedirs(results_dir, exist_ok=True)
     written = write_table(pd.DataFrame(rows), f"{results_dir}/code_traversal.feather")

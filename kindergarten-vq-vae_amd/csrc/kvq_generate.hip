@@ -133,16 +133,21 @@ struct Chunk<KVQ_F32> {
     }
 };
 
-template <int DT>
-__global__ __launch_bounds__(64) void gen_attn_kernel(const GenState* __restrict__ st, const void* __restrict__ q, int64_t ldq,
-                                                       const void* __restrict__ k_new, const void* __restrict__ v_new, int64_t ld_new,
-                                                       void* kv, int64_t ld_kv, int64_t kv_sentence_stride, int nh, int append,
-                                                       int n_keys, int Smax, void* __restrict__ out, int64_t ldo) {
+// BEAM (kvq_beam_attn): the same arithmetic, lane mapping and summation order with two indirections in the ADDRESSES.  Self-attention:
+// key j < t of row b is row j of the cache of slot anc[t & 1][b, j] (the ancestry table of beam search, [2, B, anc_ld] int32; the row
+// is staged in LDS once); the step's own rows still go to row (b, t).  Cross-attention: row b reads sentence b / rows_per_sentence.
+template <int DT, bool BEAM>
+__device__ __forceinline__ void gen_attn_body(const GenState* __restrict__ st, const void* __restrict__ q, int64_t ldq,
+                                              const void* __restrict__ k_new, const void* __restrict__ v_new, int64_t ld_new, void* kv,
+                                              int64_t ld_kv, int64_t kv_sentence_stride, int nh, int append, int n_keys, int Smax,
+                                              void* __restrict__ out, int64_t ldo, const int32_t* __restrict__ anc, int64_t anc_half,
+                                              int anc_ld, int rows_per_sentence, int n_rows) {
     typedef typename IO<DT>::elem elem;
     typedef Chunk<DT> CH;
     typedef typename CH::raw raw;
     constexpr int EPL = CH::EPL, LPR = 64 / EPL, KPI = WAVE / LPR;
     __shared__ float sc[GEN_MAX_KEYS];
+    __shared__ int slot[BEAM ? GEN_MAX_KEYS : 1];
 
     const int b = blockIdx.x / nh, h = blockIdx.x - b * nh;
     const int lane = threadIdx.x, sub = lane % LPR, grp = lane / LPR;
@@ -151,8 +156,26 @@ __global__ __launch_bounds__(64) void gen_attn_kernel(const GenState* __restrict
     const int n = append ? t + 1 : n_keys;                    // 1 .. 128
     const int col = h * 64 + sub * EPL;
 
-    const elem* kbase = reinterpret_cast<const elem*>(kv) + (size_t)b * kv_sentence_stride + col;
+    const int src = BEAM && !append ? b / rows_per_sentence : b;     // the sentence whose keys this row reads (cross-attention)
+    const elem* kbase = reinterpret_cast<const elem*>(kv) + (size_t)src * kv_sentence_stride + col;
     const elem* vbase = kbase + (size_t)nh * 64;
+    if constexpr (BEAM) {
+        if (append) {                                         // (uniform) the slots of keys 0 .. t; a slot outside the cache reads row b
+            const int32_t* arow = anc + (size_t)(t & 1) * anc_half + (size_t)b * anc_ld;
+            for (int j = lane; j < n; j += WAVE) {
+                const int s = arow[j];
+                slot[j] = s >= 0 && s < n_rows ? s : b;
+            }
+            __syncthreads();
+        }
+    }
+    // row j of the keys (of the values: + nh * 64) as this query reads it
+    auto key_row = [&](int j) -> const elem* {
+        if constexpr (BEAM) {
+            if (append) return reinterpret_cast<const elem*>(kv) + (size_t)slot[j] * kv_sentence_stride + (size_t)j * ld_kv + col;
+        }
+        return kbase + (size_t)j * ld_kv;
+    };
     const elem* knew = append ? reinterpret_cast<const elem*>(k_new) + (size_t)b * ld_new + col : kbase;
     const elem* vnew = append ? reinterpret_cast<const elem*>(v_new) + (size_t)b * ld_new + col : vbase;
     const int fresh = append ? t : -1;                        // the key whose row comes from this step's projection, not from the cache
@@ -173,7 +196,7 @@ __global__ __launch_bounds__(64) void gen_attn_kernel(const GenState* __restrict
         for (int u = 0; u < GEN_UNROLL; ++u) {
             const int j = j0 + u * KPI + grp;
             const int jc = j < n ? j : n - 1;                 // (rows past the last key: a valid row, the score is not stored)
-            r[u] = *reinterpret_cast<const raw*>(jc == fresh ? knew : kbase + (size_t)jc * ld_kv);
+            r[u] = *reinterpret_cast<const raw*>(jc == fresh ? knew : key_row(jc));
         }
 #pragma unroll
         for (int u = 0; u < GEN_UNROLL; ++u) {
@@ -211,7 +234,7 @@ __global__ __launch_bounds__(64) void gen_attn_kernel(const GenState* __restrict
         for (int u = 0; u < GEN_UNROLL; ++u) {
             const int j = j0 + u * KPI + grp;
             const int jc = j < n ? j : n - 1;
-            r[u] = *reinterpret_cast<const raw*>(jc == fresh ? vnew : vbase + (size_t)jc * ld_kv);
+            r[u] = *reinterpret_cast<const raw*>(jc == fresh ? vnew : key_row(jc) + (size_t)nh * 64);
             p[u] = j < n ? sc[jc] : 0.f;
         }
 #pragma unroll
@@ -231,6 +254,25 @@ __global__ __launch_bounds__(64) void gen_attn_kernel(const GenState* __restrict
         for (int e = 0; e < EPL; ++e) acc[e] *= inv;
         *reinterpret_cast<raw*>(reinterpret_cast<elem*>(out) + (size_t)b * ldo + col) = CH::pack(acc);
     }
+}
+
+template <int DT>
+__global__ __launch_bounds__(64) void gen_attn_kernel(const GenState* __restrict__ st, const void* __restrict__ q, int64_t ldq,
+                                                       const void* __restrict__ k_new, const void* __restrict__ v_new, int64_t ld_new,
+                                                       void* kv, int64_t ld_kv, int64_t kv_sentence_stride, int nh, int append,
+                                                       int n_keys, int Smax, void* __restrict__ out, int64_t ldo) {
+    gen_attn_body<DT, false>(st, q, ldq, k_new, v_new, ld_new, kv, ld_kv, kv_sentence_stride, nh, append, n_keys, Smax, out, ldo, nullptr, 0, 0, 1, 0);
+}
+
+template <int DT>
+__global__ __launch_bounds__(64) void beam_attn_kernel(const GenState* __restrict__ st, const void* __restrict__ q, int64_t ldq,
+                                                        const void* __restrict__ k_new, const void* __restrict__ v_new, int64_t ld_new,
+                                                        void* kv, int64_t ld_kv, int64_t kv_sentence_stride, int nh, int append,
+                                                        int n_keys, int Smax, void* __restrict__ out, int64_t ldo,
+                                                        const int32_t* __restrict__ anc, int64_t anc_half, int anc_ld, int rows_per_sentence,
+                                                        int n_rows) {
+    gen_attn_body<DT, true>(st, q, ldq, k_new, v_new, ld_new, kv, ld_kv, kv_sentence_stride, nh, append, n_keys, Smax, out, ldo, anc, anc_half,
+                            anc_ld, rows_per_sentence, n_rows);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -315,6 +357,262 @@ __global__ void gen_advance_kernel(GenState* st) { st->t += 1; }
 __global__ void gen_gumbel_debug_kernel(const unsigned* __restrict__ bits, int64_t n, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = gen_gumbel_from_bits(bits[i]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// beam search: one step of the search of one sentence per workgroup of 1024 threads (include/kvq.h "beam search")
+//
+// The 16 waves are split evenly over WT = 1, 2, 4, 8 >= W beam slots (16 / WT waves a beam), so every live beam's row of logits is
+// read ONCE, 16 bytes a lane, all beams at the same time.  A thread keeps the WT best raw logits it has seen (sorted, in registers)
+// and an online (max, sum exp) of its columns; W rounds of a wave arg-max leave each wave's best W in LDS, a second W rounds over
+// the 16 survivors of a beam its best W, and a last W rounds over the at most W * W scored survivors of the sentence the new beams.
+// Within a beam the order by logit is the order by score, so no candidate is lost.
+// f32 roundings in front of a beam's log-sum-exp, longest chain through one term: its own exponential (2 ulp), the tree of depth 3 over
+// the 8 columns of its chunk, then per further chunk of the thread one addition and at most one rescaling of the running sum (a fast
+// exponential and a product: 3), then 6 wave levels and the waves of the beam, each an exponential, a product and an addition (4):
+// kvq_beam_select refuses a V for which 4 chunks + 5 + 4 (6 + waves) exceeds 256 -- the premise of the tolerance in tests/_beam_ref.py.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int BEAM_THREADS = 1024;
+constexpr int BEAM_WAVES = BEAM_THREADS / WAVE;
+constexpr int BEAM_MAX = 8;
+constexpr int BEAM_NONE = 0x7fffffff;
+
+// (m, s) = max and sum exp(x - m) of two disjoint sets of columns; an empty set is (-inf, 0).  Symmetric in its arguments.
+__device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
+    const float M = fmaxf(m, om);
+    const float a = m == -INFINITY ? 0.f : s * __expf(m - M);
+    const float b = om == -INFINITY ? 0.f : os * __expf(om - M);
+    m = M;
+    s = a + b;
+}
+
+template <int DT, int WT>
+__global__ __launch_bounds__(BEAM_THREADS) void beam_select_kernel(const GenState* __restrict__ st, const void* __restrict__ logits,
+                                                                    int64_t ld, int V, int R, int W, int Lmax, int64_t* __restrict__ ids,
+                                                                    int32_t* __restrict__ parent, float* __restrict__ scores,
+                                                                    float* __restrict__ step_scores, int32_t* __restrict__ anc,
+                                                                    int32_t* __restrict__ finished, int32_t* __restrict__ lengths,
+                                                                    float* __restrict__ step_logits) {
+    constexpr int WPB = BEAM_WAVES / WT, TPB = WPB * WAVE;     // waves / threads that scan one beam
+    __shared__ float old_score[BEAM_MAX];
+    __shared__ int old_fin[BEAM_MAX], old_len[BEAM_MAX];
+    __shared__ float wave_x[BEAM_MAX][BEAM_WAVES][BEAM_MAX];   // [beam][wave of the beam][rank] (WPB * WT = 16 entries a beam)
+    __shared__ int wave_v[BEAM_MAX][BEAM_WAVES][BEAM_MAX];
+    __shared__ float wave_m[BEAM_MAX][BEAM_WAVES], wave_s[BEAM_MAX][BEAM_WAVES];
+    __shared__ float cand_x[BEAM_MAX][BEAM_MAX];
+    __shared__ int cand_v[BEAM_MAX][BEAM_MAX];
+    __shared__ int new_parent[BEAM_MAX];                       // the beam (0 .. nW-1) whose history new beam i continues
+
+    const int b = blockIdx.x, r0 = b * W;
+    const int nW = min(W, R - r0);                             // (the last sentence of a padded slot space may be short)
+    const int t = st->t;
+    if (t < 0 || t + 1 >= Lmax || t + 1 >= st->Lmax) return;   // (uniform) no column t + 1: nothing is stored
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int pad_id = st->pad_id, eos_id = st->eos_id;
+    const size_t half = (size_t)R * Lmax;
+    const int32_t* anc_old = anc + (size_t)(t & 1) * half;
+    int32_t* anc_new = anc + (size_t)((t + 1) & 1) * half;
+
+    if (t + 1 < st->P) {                                       // (uniform) inside the prompt: tokens, scores and histories are kept
+        for (int w = 0; w < nW; ++w) {
+            const int r = r0 + w;
+            for (int j = tid; j <= t; j += BEAM_THREADS) anc_new[(size_t)r * Lmax + j] = anc_old[(size_t)r * Lmax + j];
+            if (tid == 0) {
+                anc_new[(size_t)r * Lmax + t + 1] = r;
+                parent[(size_t)r * Lmax + t + 1] = r;
+                step_scores[(size_t)r * Lmax + t + 1] = scores[r];
+            }
+            if (step_logits)
+                for (int v = tid; v < V; v += BEAM_THREADS) step_logits[((size_t)r * Lmax + t) * V + v] = IO<DT>::load1(logits, (size_t)r * ld + v);
+        }
+        return;
+    }
+
+    // ---- everything of the old state this workgroup will overwrite is read first ----
+    if (tid < BEAM_MAX) {
+        const bool in = tid < nW;
+        old_score[tid] = in ? scores[r0 + tid] : -INFINITY;
+        old_fin[tid] = in ? finished[r0 + tid] : 1;
+        old_len[tid] = in ? lengths[r0 + tid] : 0;
+    }
+    __syncthreads();
+
+    // ---- scan: beam `beam` by the waves beam * WPB .. beam * WPB + WPB - 1 ----
+    const int beam = wave / WPB, bw = wave - beam * WPB, btid = bw * WAVE + lane;
+    const bool live = beam < nW && !old_fin[beam] && old_score[beam] > -INFINITY;      // (uniform per wave)
+    if (live) {
+        float tv[WT];
+        int ti[WT];
+#pragma unroll
+        for (int k = 0; k < WT; ++k) { tv[k] = -INFINITY; ti[k] = BEAM_NONE; }
+        float m = -INFINITY, s = 0.f;
+        bool nan = false;
+        const size_t row = (size_t)(r0 + beam) * ld;
+        float* lrow = step_logits ? step_logits + ((size_t)(r0 + beam) * Lmax + t) * V : nullptr;
+        const int nchunk = (V + 7) >> 3;                       // (ld % 8 == 0: the chunk lies inside the row)
+#pragma unroll 2
+        for (int c = btid; c < nchunk; c += TPB) {
+            const f32x8 x8 = IO<DT>::load8(logits, row + 8 * c);
+            float x[8] = {x8.lo.x, x8.lo.y, x8.lo.z, x8.lo.w, x8.hi.x, x8.hi.y, x8.hi.z, x8.hi.w};
+            float m8 = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int v = 8 * c + e;
+                if (v < V) {
+                    if (lrow) lrow[v] = x[e];
+                    nan |= x[e] != x[e];
+                    m8 = fmaxf(m8, x[e]);
+                    if (sel_better(x[e], v, tv[WT - 1], ti[WT - 1])) {      // among the thread's best WT: sorted insertion
+                        tv[WT - 1] = x[e]; ti[WT - 1] = v;
+#pragma unroll
+                        for (int k = WT - 1; k > 0; --k)
+                            if (sel_better(tv[k], ti[k], tv[k - 1], ti[k - 1])) {
+                                const float fv = tv[k]; tv[k] = tv[k - 1]; tv[k - 1] = fv;
+                                const int fi = ti[k]; ti[k] = ti[k - 1]; ti[k - 1] = fi;
+                            }
+                    }
+                } else {
+                    x[e] = -INFINITY;                          // (columns >= V never take part)
+                }
+            }
+            if (m8 > m) { s = m == -INFINITY ? 0.f : s * __expf(m - m8); m = m8; }
+            if (m > -INFINITY) {
+                float e8[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) e8[e] = __expf(x[e] - m);       // (exp(-inf) = 0: a column >= V or a logit of -inf)
+                s += ((e8[0] + e8[1]) + (e8[2] + e8[3])) + ((e8[4] + e8[5]) + (e8[6] + e8[7]));
+            }
+        }
+        // the wave's (max, sum): a butterfly, the same bits in every lane
+#pragma unroll
+        for (int k = 32; k >= 1; k >>= 1) {
+            const float om = __shfl_xor(m, k, WAVE), os = __shfl_xor(s, k, WAVE);
+            lse_merge(m, s, om, os);
+        }
+        if (__any(nan)) { m = 0.f; s = __builtin_nanf(""); }   // a NaN among the columns: the beam's scores are NaN, it offers nothing
+        if (lane == 0) { wave_m[beam][bw] = m; wave_s[beam][bw] = s; }
+        // the wave's best W: W rounds of an arg-max over the lanes' heads
+        for (int i = 0; i < W; ++i) {
+            float bv = tv[0];
+            int bi = ti[0];
+#pragma unroll
+            for (int k = 32; k >= 1; k >>= 1) {
+                const float ov = __shfl_xor(bv, k, WAVE);
+                const int oi = __shfl_xor(bi, k, WAVE);
+                if (sel_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            if (bi != BEAM_NONE && ti[0] == bi) {              // the winner's head leaves its list
+#pragma unroll
+                for (int k = 0; k + 1 < WT; ++k) { tv[k] = tv[k + 1]; ti[k] = ti[k + 1]; }
+                tv[WT - 1] = -INFINITY; ti[WT - 1] = BEAM_NONE;
+            }
+            if (lane == 0) { wave_x[beam][bw][i] = bv; wave_v[beam][bw][i] = bi; }
+        }
+    }
+    __syncthreads();
+
+    // ---- a beam's best W of its waves' W each: wave w for beam w ----
+    if (wave < nW && !old_fin[wave] && old_score[wave] > -INFINITY) {
+        const int ww = lane / WT, wi = lane % WT;              // (WPB * WT = 16 lanes hold the survivors)
+        float cv = -INFINITY;
+        int ci = BEAM_NONE;
+        if (ww < WPB && wi < W) { cv = wave_x[wave][ww][wi]; ci = wave_v[wave][ww][wi]; }
+        for (int i = 0; i < W; ++i) {
+            float bv = cv;
+            int bi = ci;
+#pragma unroll
+            for (int k = 32; k >= 1; k >>= 1) {
+                const float ov = __shfl_xor(bv, k, WAVE);
+                const int oi = __shfl_xor(bi, k, WAVE);
+                if (sel_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            if (bi != BEAM_NONE && ci == bi) { cv = -INFINITY; ci = BEAM_NONE; }
+            if (lane == 0) { cand_x[wave][i] = bv; cand_v[wave][i] = bi; }
+        }
+    }
+    __syncthreads();
+
+    // ---- the sentence's best W of the scored survivors: wave 0, lane = (beam, rank) ----
+    if (wave == 0) {
+        const int w = lane / BEAM_MAX, i = lane % BEAM_MAX;
+        float cs = -INFINITY;                                  // the candidate's score; the key of a tie is (beam << 28) | token
+        int ck = BEAM_NONE;
+        if (w < nW && i < W && old_score[w] > -INFINITY) {
+            if (old_fin[w]) {
+                if (i == 0) { cs = old_score[w]; ck = w << 28; }            // a finished beam: itself, ranking as (w, 0)
+            } else if (cand_v[w][i] != BEAM_NONE) {
+                float m = wave_m[w][0], s = wave_s[w][0];
+                for (int k = 1; k < WPB; ++k) lse_merge(m, s, wave_m[w][k], wave_s[w][k]);
+                const float lse = m + logf(s);
+                const float lp = cand_x[w][i] - lse;
+                const float sc = old_score[w] + lp;
+                if (sc > -INFINITY) { cs = sc; ck = (w << 28) | cand_v[w][i]; }         // (a NaN or -inf score is no candidate)
+            }
+        }
+        float win_s = -INFINITY;
+        int win_k = BEAM_NONE;
+        for (int n = 0; n < nW; ++n) {
+            float bv = cs;
+            int bk = ck;
+#pragma unroll
+            for (int k = 32; k >= 1; k >>= 1) {
+                const float ov = __shfl_xor(bv, k, WAVE);
+                const int ok = __shfl_xor(bk, k, WAVE);
+                if (sel_better(ov, ok, bv, bk)) { bv = ov; bk = ok; }
+            }
+            if (bk != BEAM_NONE && ck == bk) { cs = -INFINITY; ck = BEAM_NONE; }
+            if (lane == n) { win_s = bv; win_k = bk; }
+        }
+        if (lane < nW) {                                       // new beam `lane` of the sentence
+            const int r = r0 + lane;
+            const size_t at = (size_t)r * Lmax + t + 1;
+            if (win_k == BEAM_NONE) {                          // fewer candidates than beams: a dead beam
+                ids[at] = pad_id;
+                parent[at] = r;
+                scores[r] = -INFINITY;
+                step_scores[at] = -INFINITY;
+                finished[r] = 1;
+                new_parent[lane] = lane;
+            } else {
+                const int w = win_k >> 28, v = win_k & ((1 << 28) - 1);
+                const bool was = old_fin[w] != 0;
+                ids[at] = was ? pad_id : v;
+                parent[at] = r0 + w;
+                scores[r] = win_s;
+                step_scores[at] = win_s;
+                const bool ends = !was && v == eos_id;
+                finished[r] = was || ends ? 1 : 0;
+                lengths[r] = ends ? t + 2 : old_len[w];
+                new_parent[lane] = w;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- histories: the parent's row of the old half, extended by the new row itself ----
+    for (int i = 0; i < nW; ++i) {
+        const int32_t* src = anc_old + (size_t)(r0 + new_parent[i]) * Lmax;
+        int32_t* dst = anc_new + (size_t)(r0 + i) * Lmax;
+        for (int j = tid; j <= t; j += BEAM_THREADS) dst[j] = src[j];
+        if (tid == 0) dst[t + 1] = r0 + i;
+    }
+}
+
+// hypotheses from slot space: out[r, j] = ids[anc[t & 1][r, j], j] for j < lengths[r] (and j <= t), pad_id behind
+__global__ __launch_bounds__(256) void beam_gather_kernel(const GenState* __restrict__ st, const int64_t* __restrict__ ids,
+                                                           const int32_t* __restrict__ anc, const int32_t* __restrict__ lengths, int R,
+                                                           int Lmax, int64_t* __restrict__ out) {
+    const int t = st->t;
+    if (t < 0 || t >= Lmax || t >= st->Lmax) return;           // (uniform)
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)R * Lmax) return;
+    const int r = (int)(e / Lmax), j = (int)(e - (int64_t)r * Lmax);
+    int64_t tok = st->pad_id;
+    if (j < lengths[r] && j <= t) {
+        const int s = anc[(size_t)(t & 1) * R * Lmax + e];
+        tok = ids[(size_t)(s >= 0 && s < R ? s : r) * Lmax + j];
+    }
+    out[e] = tok;
 }
 
 }  // namespace kvq
@@ -402,6 +700,90 @@ int kvq_gen_select(const void* state, const void* logits, int64_t ld, int V, int
         hipLaunchKernelGGL(gen_select_kernel<KVQ_BF16>, dim3((unsigned)B), dim3(SEL_THREADS), 0, s, gs, logits, ld, V, ids, finished, lengths,
                            step_logits);
     return check_launch("gen_select_kernel");
+}
+
+int kvq_beam_attn(const void* state, const void* q, int64_t ldq, const void* k_new, const void* v_new, int64_t ld_new, void* kv,
+                  int64_t ld_kv, int64_t kv_sentence_stride, int R, int nh, int append, int n_keys, int Smax, const int32_t* anc,
+                  int anc_ld, int rows_per_sentence, int io_dtype, void* out, int64_t ldo, void* stream) {
+    KVQ_REQUIRE(state && q && kv && out, "kvq_beam_attn: null pointer argument");
+    KVQ_REQUIRE(io_dtype == KVQ_F32 || io_dtype == KVQ_BF16, "kvq_beam_attn: unsupported io dtype %d", io_dtype);
+    KVQ_REQUIRE(R > 0 && nh > 0 && (int64_t)R * nh < (1ll << 31), "kvq_beam_attn: R and nh must be positive (R=%d nh=%d)", R, nh);
+    const int64_t W = (int64_t)nh * 64;
+    const int epl = io_dtype == KVQ_BF16 ? 8 : 4;
+    KVQ_REQUIRE(ldq >= W && ldo >= W && ld_kv >= 2 * W, "kvq_beam_attn: leading dimension below the %lld columns of %d heads", (long long)W, nh);
+    KVQ_REQUIRE(ldq % epl == 0 && ldo % epl == 0 && ld_kv % epl == 0 && kv_sentence_stride % epl == 0,
+                "kvq_beam_attn: every stride must be a multiple of 16 bytes");
+    KVQ_REQUIRE((((uintptr_t)q | (uintptr_t)kv | (uintptr_t)out) & 15) == 0 && ((uintptr_t)state & 7) == 0,
+                "kvq_beam_attn: 16-byte aligned q, kv and out (8-byte aligned state) required");
+    if (append) {
+        KVQ_REQUIRE(k_new && v_new && (((uintptr_t)k_new | (uintptr_t)v_new) & 15) == 0 && ld_new >= W && ld_new % epl == 0,
+                    "kvq_beam_attn: append needs 16-byte aligned k_new / v_new rows of at least %lld columns", (long long)W);
+        KVQ_REQUIRE(Smax >= 1 && Smax <= GEN_MAX_KEYS, "kvq_beam_attn: Smax=%d outside 1..%d", Smax, GEN_MAX_KEYS);
+        KVQ_REQUIRE(kv_sentence_stride >= (int64_t)Smax * ld_kv, "kvq_beam_attn: a row of the cache holds fewer than Smax=%d positions", Smax);
+        KVQ_REQUIRE(anc && ((uintptr_t)anc & 3) == 0 && anc_ld >= Smax, "kvq_beam_attn: append needs the ancestry table [2, R, anc_ld >= Smax=%d]", Smax);
+    } else {
+        KVQ_REQUIRE(n_keys >= 1 && n_keys <= GEN_MAX_KEYS, "kvq_beam_attn: n_keys=%d outside 1..%d", n_keys, GEN_MAX_KEYS);
+        KVQ_REQUIRE(kv_sentence_stride >= (int64_t)n_keys * ld_kv, "kvq_beam_attn: a sentence holds fewer than n_keys=%d rows", n_keys);
+        KVQ_REQUIRE(rows_per_sentence >= 1, "kvq_beam_attn: rows_per_sentence=%d must be positive", rows_per_sentence);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const GenState* gs = reinterpret_cast<const GenState*>(state);
+    dim3 grid((unsigned)(R * nh));
+    const int64_t half = (int64_t)R * anc_ld;
+    if (io_dtype == KVQ_F32)
+        hipLaunchKernelGGL(beam_attn_kernel<KVQ_F32>, grid, dim3(64), 0, s, gs, q, ldq, k_new, v_new, ld_new, kv, ld_kv, kv_sentence_stride, nh,
+                           append, n_keys, Smax, out, ldo, anc, half, anc_ld, rows_per_sentence, R);
+    else
+        hipLaunchKernelGGL(beam_attn_kernel<KVQ_BF16>, grid, dim3(64), 0, s, gs, q, ldq, k_new, v_new, ld_new, kv, ld_kv, kv_sentence_stride, nh,
+                           append, n_keys, Smax, out, ldo, anc, half, anc_ld, rows_per_sentence, R);
+    return check_launch("beam_attn_kernel");
+}
+
+int kvq_beam_select(const void* state, const void* logits, int64_t ld, int V, int R, int W, int Lmax, int io_dtype, int64_t* ids,
+                    int32_t* parent, float* scores, float* step_scores, int32_t* anc, int32_t* finished, int32_t* lengths,
+                    float* step_logits, void* stream) {
+    KVQ_REQUIRE(state && logits && ids && parent && scores && step_scores && anc && finished && lengths, "kvq_beam_select: null pointer argument");
+    KVQ_REQUIRE(io_dtype == KVQ_F32 || io_dtype == KVQ_BF16, "kvq_beam_select: unsupported io dtype %d", io_dtype);
+    KVQ_REQUIRE(R > 0 && V > 0 && ld >= V && Lmax > 0, "kvq_beam_select: R, V, Lmax must be positive and ld >= V (R=%d V=%d ld=%lld)", R, V, (long long)ld);
+    KVQ_REQUIRE(W >= 1 && W <= BEAM_MAX && W <= V, "kvq_beam_select: W=%d outside 1..%d or above V=%d", W, BEAM_MAX, V);
+    KVQ_REQUIRE(ld % 8 == 0 && ((uintptr_t)logits & 15) == 0, "kvq_beam_select: ld %% 8 == 0 and 16-byte aligned logits required");
+    KVQ_REQUIRE(((uintptr_t)state & 7) == 0 && ((uintptr_t)ids & 7) == 0
+                    && (((uintptr_t)parent | (uintptr_t)scores | (uintptr_t)step_scores | (uintptr_t)anc | (uintptr_t)finished | (uintptr_t)lengths
+                         | (uintptr_t)step_logits) & 3) == 0,
+                "kvq_beam_select: misaligned state, ids or int32 / f32 buffers");
+    const int WT = W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 4 : 8, waves = BEAM_WAVES / WT;
+    const int chunks = ((V + 7) / 8 + waves * WAVE - 1) / (waves * WAVE);          // of one thread
+    KVQ_REQUIRE(V < (1 << 28) && 4 * chunks + 5 + 4 * (6 + waves) <= 256,
+                "kvq_beam_select: V=%d with W=%d puts more than 256 roundings in front of a log-sum-exp (the bound of its tolerance)", V, W);
+    hipStream_t s = (hipStream_t)stream;
+    const GenState* gs = reinterpret_cast<const GenState*>(state);
+    dim3 grid((unsigned)((R + W - 1) / W));
+    auto go = [&](auto dt, auto wt) {
+        constexpr int DT = decltype(dt)::value, WTc = decltype(wt)::value;
+        hipLaunchKernelGGL((beam_select_kernel<DT, WTc>), grid, dim3(BEAM_THREADS), 0, s, gs, logits, ld, V, R, W, Lmax, ids, parent, scores, step_scores,
+                           anc, finished, lengths, step_logits);
+    };
+    auto with_dt = [&](auto dt) {
+        if (WT == 1) go(dt, std::integral_constant<int, 1>());
+        else if (WT == 2) go(dt, std::integral_constant<int, 2>());
+        else if (WT == 4) go(dt, std::integral_constant<int, 4>());
+        else go(dt, std::integral_constant<int, 8>());
+    };
+    if (io_dtype == KVQ_F32) with_dt(std::integral_constant<int, KVQ_F32>());
+    else with_dt(std::integral_constant<int, KVQ_BF16>());
+    return check_launch("beam_select_kernel");
+}
+
+int kvq_beam_gather(const void* state, const int64_t* ids, const int32_t* anc, const int32_t* lengths, int R, int Lmax, int64_t* out,
+                    void* stream) {
+    KVQ_REQUIRE(state && ids && anc && lengths && out, "kvq_beam_gather: null pointer argument");
+    KVQ_REQUIRE(R > 0 && Lmax > 0, "kvq_beam_gather: R and Lmax must be positive (R=%d Lmax=%d)", R, Lmax);
+    KVQ_REQUIRE(((uintptr_t)state & 7) == 0 && (((uintptr_t)ids | (uintptr_t)out) & 7) == 0 && (((uintptr_t)anc | (uintptr_t)lengths) & 3) == 0,
+                "kvq_beam_gather: misaligned buffers");
+    const int64_t n = (int64_t)R * Lmax;
+    hipLaunchKernelGGL(beam_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const GenState*>(state), ids, anc, lengths, R, Lmax, out);
+    return check_launch("beam_gather_kernel");
 }
 
 int kvq_gen_advance(void* state, void* stream) {

@@ -169,6 +169,9 @@ SIGNATURES = {
     "kvq_gen_select": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "kvq_gen_gumbel_debug": (_int, [_vp, _i64, _vp, _vp]),
     "kvq_gen_advance": (_int, [_vp, _vp]),
+    "kvq_beam_attn": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _int, _int, _vp, _int, _int, _int, _vp, _i64, _vp]),
+    "kvq_beam_select": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "kvq_beam_gather": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
 }
 
 _lib = None
@@ -209,7 +212,8 @@ _FAMILIES = (("kvq_gemm_", "gemm"), ("kvq_attn_", "attention"), ("kvq_dropout_re
              ("kvq_embed_ln_fwd", "layernorm"), ("kvq_ce_", "loss"), ("kvq_seq_acc", "loss"), ("kvq_adam_", "adam"),
              ("kvq_step_state_", "adam"), ("kvq_grad_", "adam"), ("kvq_accum_", "adam"), ("kvq_weight_ema_", "adam"), ("kvq_vq_", "vq"), ("kvq_gumbel_", "vq"), ("kvq_fp8_", "fp8_quantize"), ("kvq_reduce_batch", "reduce"),
              ("kvq_colsum", "reduce"), ("kvq_sum_slabs", "reduce"), ("kvq_gelu_", "gelu"), ("kvq_embed_grad", "embedding_grad"),
-             ("kvq_zero_ranges", "embedding_grad"), ("kvq_gen_attn", "generate_attention"), ("kvq_gen_", "generate_other"))
+             ("kvq_zero_ranges", "embedding_grad"), ("kvq_gen_attn", "generate_attention"), ("kvq_gen_", "generate_other"),
+             ("kvq_beam_attn", "generate_attention"), ("kvq_beam_", "generate_other"))
 _fam = None          # None = off; else dict(events=[(family, e0, e1)], cal=[(e0, e1)])
 
 

@@ -655,6 +655,7 @@ class TrainEngine:
         self.aux = []
         self._bufs = {}
         self._gen_cache = {}              # generate(): buffers and captured step per (B, Se, max_length, want_logits)
+        self._beam_cache = {}             # beam_search(): the same per (B, Se, max_length, num_beams, want_trace)
 
         def add_aux(p, name):
             a = dict(name=name, p=p, g=torch.zeros_like(p.data), m=torch.zeros_like(p.data), v=torch.zeros_like(p.data),
@@ -1928,19 +1929,24 @@ class TrainEngine:
 
     def _gen_step(self, g):
         """One position: the decoder layer schedule of _fb_gen on [Bp, H] rows, the token at column t in, the token at t + 1 out.
-        Launches only (no host read): the body of the captured graph, and what graph=False runs max_length - 1 times."""
+        Launches only (no host read): the body of the captured graph, and what graph=False runs max_length - 1 times.
+        With g["W"] (beam_search: the rows are slot space) the two attention calls follow the ancestry
+        table and the selection is a step of the search; everything else is the same launch on R rows."""
         fl, H, nh, dcfg = self.flat, self.H, self.nh, self.dcfg
-        eps, st = dcfg.layer_norm_eps, g["state"]
+        eps, st, W = dcfg.layer_norm_eps, g["state"], g.get("W")
         x = nnops.gen_embed(st, g["ids"], fl.w("dec.emb.word"), fl.w("dec.emb.pos"), fl.w("dec.emb.type")[0], fl.w32("dec.emb.ln.w"),
                             fl.w32("dec.emb.ln.b"), eps)
         for i in range(self.n_dec_layers):
             pre = f"dec.{i}.sa."
             qkv = self._linear(x, None, None, fused=([pre + "q.w", pre + "k.w", pre + "v.w"], [pre + "q.b", pre + "k.b", pre + "v.b"]))
-            ctx = nnops.gen_attn_self(st, qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], g["cache"][i], nh)
+            if W is None:
+                ctx = nnops.gen_attn_self(st, qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], g["cache"][i], nh)
+            else:
+                ctx = nnops.beam_attn_self(st, qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], g["cache"][i], g["anc"], nh)
             x = self._dense_residual_ln(ctx, pre + "o.w", pre + "o.b", x, pre + "ln.w", pre + "ln.b", eps, 0.0, 0)[0]
             pre = f"dec.{i}.ca."
             q = self._linear(x, pre + "q.w", pre + "q.b")
-            ctx = nnops.gen_attn_cross(st, q, g["kv"][i], g["Se"], nh)
+            ctx = nnops.gen_attn_cross(st, q, g["kv"][i], g["Se"], nh) if W is None else nnops.beam_attn_cross(st, q, g["kv"][i], g["Se"], nh, W)
             x = self._dense_residual_ln(ctx, pre + "o.w", pre + "o.b", x, pre + "ln.w", pre + "ln.b", eps, 0.0, 0)[0]
             pre = f"dec.{i}."
             a = self._linear_gelu(x, pre + "f1.w", pre + "f1.b")[1]
@@ -1950,7 +1956,11 @@ class TrainEngine:
         Wv = fl.w("dec.emb.word", rows=self.Vp)
         bv = fl.shadow[fl.seg["head.bias"][0]: fl.seg["head.bias"][0] + self.Vp]
         logits = self._linear(hN, None, None, Wb=(Wv, bv), key="dec.emb.word")                      # [Bp, Vp]
-        nnops.gen_select(st, logits, self.V, g["ids"], g["finished"], g["lengths"], g["step_logits"])      # (temperature, seed: in the state)
+        if W is None:
+            nnops.gen_select(st, logits, self.V, g["ids"], g["finished"], g["lengths"], g["step_logits"])  # (temperature, seed: in the state)
+        else:
+            nnops.beam_select(st, logits, self.V, W, g["ids"], g["parent"], g["scores"], g["step_scores"], g["anc"], g["finished"],
+                              g["lengths"], g["step_logits"])
         nnops.gen_advance(st)
 
     def _gen_buffers(self, B, Se, L, want_logits, graph):
@@ -2008,11 +2018,11 @@ class TrainEngine:
         return graph
 
     def gen_census(self):
-        """Per captured generation step: {kind: nodes} (kvq_graph_census), as _StepGraphs.node_census."""
+        """Per captured generation step (generate's, then beam_search's): {kind: nodes} (kvq_graph_census), as _StepGraphs.node_census."""
         import ctypes
         kinds = ("kernel", "memset", "memcpy", "empty", "event", "other")
         out = []
-        for g in self._gen_cache.values():
+        for g in list(self._gen_cache.values()) + list(self._beam_cache.values()):
             if g["graph"] is not None:
                 counts = (ctypes.c_int64 * len(kinds))()
                 check(lib().kvq_graph_census(g["graph"].raw_cuda_graph(), counts), "kvq_graph_census")
@@ -2094,14 +2104,159 @@ class TrainEngine:
         self._latent_call("generate_codes")         # every refusal above and in here comes before the lookup's launch
         return self.generate(self.codes_to_latents(rows), max_length, prompt_ids, **kw)
 
+    # ------------------------------------------------------------------------------------------------------------
+    # beam search: the same step on R = round_up(B W, 8) rows of slot space
+    # ------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_beams(num_beams, length_penalty, V):
+        """What beam_search refuses beyond generate's refusals; needs no device."""
+        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= nnops.BEAM_MAX or num_beams > V:
+            raise KvqError(f"TrainEngine.beam_search: num_beams must be an int in 1 .. {min(nnops.BEAM_MAX, V)}, got {num_beams!r}")
+        if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or not math.isfinite(length_penalty):
+            raise KvqError(f"TrainEngine.beam_search: length_penalty must be a finite number, got {length_penalty!r}")
+
+    def _beam_buffers(self, B, Se, L, W, want_trace, graph):
+        """_gen_buffers in slot space: beam w of sentence b is row b W + w of R = round_up(B W, 8) rows; S = ceil(R / W) sentences
+        of latents (zero behind B: the pad rows read valid memory).  The captured step is _gen_step with g["W"]."""
+        cache = self._beam_cache
+        key = (B, Se, L, W, bool(want_trace), self.flat.shadow.data_ptr())
+        g = cache.get(key)
+        if g is None:
+            dev, H, nl = self.dev, self.H, self.n_dec_layers
+            R = _round_up(B * W, 8)
+            S = -(-R // W)
+            own = torch.arange(R, dtype=torch.int32, device=dev)
+            g = dict(B=B, R=R, S=S, W=W, Se=Se, L=L, graph=None, replays=0,
+                     state=nnops.new_gen_state(dev, 0, 1, L, None, 0),
+                     ids=torch.zeros((R, L), dtype=torch.int64, device=dev), hyp=torch.zeros((R, L), dtype=torch.int64, device=dev),
+                     own=own.view(R, 1).expand(R, L).contiguous(),
+                     parent=torch.zeros((R, L), dtype=torch.int32, device=dev), anc=torch.zeros((2, R, L), dtype=torch.int32, device=dev),
+                     scores=torch.zeros(R, dtype=torch.float32, device=dev), step_scores=torch.zeros((R, L), dtype=torch.float32, device=dev),
+                     finished=torch.zeros(R, dtype=torch.int32, device=dev), lengths=torch.zeros(R, dtype=torch.int32, device=dev),
+                     cache=[torch.zeros((R, L, 2 * H), dtype=self.dtype, device=dev) for _ in range(nl)],
+                     lat=torch.zeros((S, Se, H), dtype=self.dtype, device=dev),
+                     step_logits=torch.zeros((R, L, self.V), dtype=torch.float32, device=dev) if want_trace else None)
+            if self._cakv_batched:
+                g["kv_all"] = torch.empty((S * Se, nl * 2 * H), dtype=self.dtype, device=dev)
+                g["kv"] = [g["kv_all"][:, 2 * H * i: 2 * H * (i + 1)] for i in range(nl)]
+            else:
+                g["kv"] = [torch.empty((S * Se, 2 * H), dtype=self.dtype, device=dev) for _ in range(nl)]
+            while len(cache) >= self._GEN_GRAPHS_KEPT:
+                cache.pop(next(iter(cache)))
+            cache[key] = g
+        if graph and g["graph"] is None and L > 1:
+            self._beam_reset(g, 1, None, 0)
+            self._gen_step(g)                       # once eagerly, as _gen_buffers
+            g["graph"] = self._gen_capture(g)
+        return g
+
+    def _beam_reset(self, g, P, eos_id, pad, prompt_ids=None):
+        """The start of a search: position 0, every history the identity, beam 0 of a sentence alive with score 0 and the others
+        dead (-inf: the first free step then draws W distinct tokens from one row), the rows behind B W finished and dead."""
+        B, W, L = g["B"], g["W"], g["L"]
+        g["state"].copy_(torch.tensor(nnops.gen_state_words(0, P, L, eos_id, pad, 0.0, 0), dtype=torch.int32), non_blocking=False)
+        g["ids"].fill_(pad)
+        if prompt_ids is not None:
+            g["ids"][:B * W, :P].copy_(prompt_ids.repeat_interleave(W, dim=0))
+        g["anc"].copy_(g["own"].unsqueeze(0).expand(2, -1, -1))
+        g["parent"].copy_(g["own"])
+        g["step_scores"].zero_()
+        g["scores"].fill_(float("-inf"))
+        g["scores"][:B * W:W].zero_()
+        g["finished"].zero_()
+        g["finished"][B * W:].fill_(1)
+        g["lengths"].fill_(L)
+        if g["step_logits"] is not None:
+            g["step_logits"].zero_()
+
+    def beam_search(self, latents, max_length, prompt_ids, num_beams, eos_id=None, pad_id=None, length_penalty=0.0, quantize=False,
+                    want_trace=False, graph=True):
+        """The num_beams most probable continuations of the prompt under the free-running decoder of generate(): at every position
+        the W = num_beams best of the live hypotheses' W V one-token extensions (by the sum of log-probabilities, ties to the lower
+        beam, then the lower token) survive; a hypothesis that chooses eos_id is finished, keeps its score and keeps competing.
+        The caches are never reordered: every row writes its own cache row once and reads its history through an ancestry table
+        (kvq_beam_attn, kvq_beam_select).  No host read inside the loop; graph=True replays one captured step.
+        The hypotheses are ranked once, at the end, by score / n^length_penalty (n = generated tokens, at least 1; f64, stable, -inf
+        last); pruning inside the search is by the raw sum.  Returns dict(ids [B, L], lengths [B], finished [B]: the best
+        hypothesis; beam_ids [B, W, L], beam_scores [B, W] f32 (raw sums), beam_lengths [B, W], beam_finished [B, W]: best first
+        [, trace = dict(ids, parent, step_scores [B, W, L], logits [B, W, L - 1, V] f32), in slot space] [, indices])."""
+        self._latent_call("beam_search", refresh=False)
+        self._check_beams(num_beams, length_penalty, self.V)
+        self._check_generate(latents, max_length, prompt_ids, self.H, self.dtype, self.dev, int(self.dcfg.max_position_embeddings), 0.0,
+                             V=self.V, eos_id=eos_id, pad_id=pad_id)
+        if quantize and not self.has_vq:
+            raise KvqError("TrainEngine.beam_search: quantize=True, but the model has no quantiser")
+        B, Se, _ = latents.shape
+        L, P, W = int(max_length), prompt_ids.shape[1], int(num_beams)
+        self._seq_limit("beam_search", Se, L)
+        self._latent_call("beam_search")
+        res = {}
+        if quantize:                                # the quantiser in evaluation mode, as generate(quantize=True)
+            one = torch.zeros((B, 1), dtype=torch.int64, device=self.dev)
+            q = self.forward_backward(None, None, training=False, compute_grads=False, dec_ids=one, dec_mask=torch.ones_like(one),
+                                      quantizer_training=False, stop_after_quantizer=True, want_latents=True, latents=latents)
+            latents, res["indices"] = q["z_q"].reshape(B, Se, self.H), q["indices"]
+        with torch.no_grad():
+            g = self._beam_buffers(B, Se, L, W, want_trace, graph)
+            R, S = g["R"], g["S"]
+            # ---- once per call: the cross-attention keys | values of every layer, once per SENTENCE; the start of the search ----
+            g["lat"][:B].copy_(latents)
+            lat = g["lat"].view(S * Se, self.H)
+            fl = self.flat
+            if self._cakv_batched:
+                g["kv_all"].copy_(self._linear(lat, None, None, Wb=(fl.fused(self._cakv_w, fl.shadow), fl.fused(self._cakv_b, fl.shadow)),
+                                               key=self._cakv_w[0]))
+            else:
+                for i in range(self.n_dec_layers):
+                    pre = f"dec.{i}.ca."
+                    g["kv"][i].copy_(self._linear(lat, None, None, fused=([pre + "k.w", pre + "v.w"], [pre + "k.b", pre + "v.b"])))
+            pad = (self._pad_idx if self._pad_idx is not None else 0) if pad_id is None else int(pad_id)
+            self._beam_reset(g, P, eos_id, pad, prompt_ids)
+            # ---- per position ----
+            for _ in range(L - 1):
+                if graph:
+                    g["graph"].replay()
+                else:
+                    self._gen_step(g)
+            g["replays"] += (L - 1) if graph else 0
+            # ---- once per call: hypotheses out of slot space, the final ranking ----
+            live = slice(0, B * W)
+            hyp = nnops.beam_gather(g["state"], g["ids"], g["anc"], g["lengths"], out=g["hyp"])[live].view(B, W, L)
+            scores, lengths = g["scores"][live].view(B, W), g["lengths"][live].view(B, W).long()
+            n = (lengths - P).clamp(min=1).double()
+            order = torch.sort(scores.double() / n.pow(float(length_penalty)), dim=1, descending=True, stable=True).indices
+            res.update(beam_ids=hyp.gather(1, order.unsqueeze(-1).expand(B, W, L)), beam_scores=scores.gather(1, order),
+                       beam_lengths=lengths.gather(1, order), beam_finished=(g["finished"][live].view(B, W) != 0).gather(1, order))
+            res.update(ids=res["beam_ids"][:, 0].clone(), lengths=res["beam_lengths"][:, 0].clone(), finished=res["beam_finished"][:, 0].clone())
+            if want_trace:
+                res["trace"] = dict(ids=g["ids"][live].view(B, W, L).clone(), parent=g["parent"][live].view(B, W, L).clone(),
+                                    step_scores=g["step_scores"][live].view(B, W, L).clone(),
+                                    logits=g["step_logits"][live].view(B, W, L, self.V)[:, :, :L - 1].clone())
+        return res
+
+    def beam_search_codes(self, indices, max_length, prompt_ids, num_beams, **kw):
+        """beam_search() of the codebook rows of `indices` [B, Se] / [B, Se, G] int64: as generate_codes is to generate."""
+        if kw.get("quantize"):
+            raise KvqError("TrainEngine.beam_search_codes: the latents are codebook rows already (quantize=True has nothing to do)")
+        self._latent_call("beam_search_codes", refresh=False)
+        rows = self._code_rows("beam_search_codes", indices)
+        self._check_beams(num_beams, kw.get("length_penalty", 0.0), self.V)
+        self._check_generate_call(rows.shape[0], max_length, prompt_ids, self.dev, int(self.dcfg.max_position_embeddings), 0.0, V=self.V,
+                                  eos_id=kw.get("eos_id"), pad_id=kw.get("pad_id"))
+        self._seq_limit("beam_search", rows.shape[1], max_length)
+        self._latent_call("beam_search_codes")      # every refusal above and in here comes before the lookup's launch
+        return self.beam_search(self.codes_to_latents(rows), max_length, prompt_ids, num_beams, **kw)
+
     def traverse_codes(self, enc_ids, enc_mask, sentence, position, dec_ids=None, dec_mask=None, factor=0, free_running=False,
-                       max_length=None, start_id=None):
+                       max_length=None, start_id=None, num_beams=1, length_penalty=0.0):
         """Every code at one place of one sentence: encodes the batch, takes sentence `sentence`'s own index rows [Se, G], builds the
         K variants that differ from them only at (position, factor) -- variant k carries code k there -- and decodes them with
         that sentence's decoder ids (default: its encoder ids), at most 256 variants per launch sequence.
         free_running=True: the variants are GENERATED (generate_codes, greedy) from start_id (default: the first decoder id of the
-        sentence) up to max_length (default: the decoder ids' length) instead of decoded against the sentence's own ids.
-        Returns dict(recon_ids [K, Sd], own_code (int), changed [K, Sd] bool: tokens that differ from the own code's row)."""
+        sentence) up to max_length (default: the decoder ids' length) instead of decoded against the sentence's own ids;
+        num_beams > 1: each variant's row is the best hypothesis of beam_search_codes (length_penalty: its final ranking).
+        Returns dict(recon_ids [K, Sd], own_code (int), changed [K, Sd] bool: tokens that differ from the own code's row
+        [, beam_ids [K, W, Sd], beam_scores [K, W]: every variant's hypotheses, best first, with num_beams = W > 1])."""
         self._latent_call("traverse_codes")
         if self.vq_kind not in ("VectorQuantizer", "MultiVectorQuantizer"):
             raise KvqError(f"TrainEngine.traverse_codes: needs a VectorQuantizer or MultiVectorQuantizer codebook (this model has "
@@ -2119,20 +2274,28 @@ class TrainEngine:
         K = self.K
         rows = own.unsqueeze(0).repeat(K, 1, 1)
         rows[:, int(position), int(factor)] = torch.arange(K, dtype=torch.int64, device=self.dev)
-        recon = []
+        recon, beams = [], []
         for k0 in range(0, K, self._TRAVERSE_CHUNK):
             n = min(self._TRAVERSE_CHUNK, K - k0)
             if free_running:
                 start = int(d_ids[int(sentence), 0].item()) if start_id is None else int(start_id)
-                out = self.generate_codes(rows[k0:k0 + n], int(d_ids.shape[1] if max_length is None else max_length),
-                                          torch.full((n, 1), start, dtype=torch.int64, device=self.dev))
+                gen_args = (rows[k0:k0 + n], int(d_ids.shape[1] if max_length is None else max_length),
+                            torch.full((n, 1), start, dtype=torch.int64, device=self.dev))
+                if num_beams == 1:
+                    out = self.generate_codes(*gen_args)
+                else:
+                    out = self.beam_search_codes(*gen_args, num_beams, length_penalty=length_penalty)
+                    beams.append((out["beam_ids"], out["beam_scores"]))
                 recon.append(out["ids"])
                 continue
             out = self.decode_codes(rows[k0:k0 + n], d_ids[int(sentence)].unsqueeze(0).expand(n, -1).contiguous(),
                                     d_mask[int(sentence)].unsqueeze(0).expand(n, -1).contiguous())
             recon.append(out["recon_ids"])
         recon = torch.cat(recon)
-        return dict(recon_ids=recon, own_code=own_code, changed=recon != recon[own_code].unsqueeze(0))
+        res = dict(recon_ids=recon, own_code=own_code, changed=recon != recon[own_code].unsqueeze(0))
+        if beams:
+            res.update(beam_ids=torch.cat([b[0] for b in beams]), beam_scores=torch.cat([b[1] for b in beams]))
+        return res
 
     def _forward_backward(self, input_ids, attention_mask, training, compute_grads, dec_ids=None, dec_mask=None, want_logits=False,
                           defer=False, target_ids=None, latents=None, stop_after_encoder=False, skip_quantizer=False,

@@ -1242,3 +1242,99 @@ def clock_mhz(p0, p1):
         return None, {}
     v = sorted(per.values())
     return v[len(v) // 2], per
+
+
+# ---- beam search (include/kvq.h "beam search"; csrc/kvq_generate.hip) ---------------------------------------------------------------
+BEAM_MAX = 8
+
+
+def _beam_anc(who, anc, R):
+    if anc.dim() != 3 or anc.dtype != torch.int32 or anc.shape[0] != 2 or anc.shape[1] != R or not anc.is_contiguous():
+        raise KvqError(f"kvq.nnops.{who}: the ancestry table must be a contiguous int32 [2, R = {R}, Lmax] tensor")
+    return anc.shape[2]
+
+
+def beam_attn_self(state, q, k_new, v_new, cache, anc, nh, out=None):
+    """gen_attn_self in slot space: row r stores its k_new | v_new to cache row (r, t) and attends over keys 0 .. t, key j < t read
+    from cache row (anc[t & 1][r, j], j) -- the beam's history, never a copy of the cache.  anc [2, R, Lmax] int32."""
+    require_gpu(q, k_new, v_new, cache, anc)
+    R, W = q.shape[0], nh * 64
+    ldq, ldn = _gen_rows("beam_attn_self", q, "q"), _gen_rows("beam_attn_self", k_new, "k_new")
+    if _gen_rows("beam_attn_self", v_new, "v_new") != ldn or k_new.shape != (R, W) or v_new.shape != (R, W) or q.shape[1] != W:
+        raise KvqError(f"kvq.nnops.beam_attn_self: q, k_new, v_new must be [R, {W}] and k_new, v_new share a row stride")
+    if cache.dim() != 3 or cache.shape[0] != R or cache.shape[2] != 2 * W or not cache.is_contiguous() or cache.dtype != q.dtype:
+        raise KvqError(f"kvq.nnops.beam_attn_self: the cache must be a contiguous [R, Smax, {2 * W}] tensor of q's dtype")
+    if _beam_anc("beam_attn_self", anc, R) < cache.shape[1]:
+        raise KvqError("kvq.nnops.beam_attn_self: the ancestry table holds fewer positions than the cache")
+    if out is None:
+        out = torch.empty((R, W), dtype=q.dtype, device=q.device)
+    check(lib().kvq_beam_attn(_gen_ptr(state), q.data_ptr(), ldq, k_new.data_ptr(), v_new.data_ptr(), ldn, cache.data_ptr(), cache.stride(1),
+                              cache.stride(0), R, nh, 1, 0, cache.shape[1], anc.data_ptr(), anc.shape[2], 1, io_dtype_of(q), out.data_ptr(),
+                              _gen_rows("beam_attn_self", out, "out"), stream_ptr()), "kvq_beam_attn")
+    return out
+
+
+def beam_attn_cross(state, q, kv, n_keys, nh, rows_per_sentence, out=None):
+    """gen_attn_cross for rows_per_sentence query rows a sentence: row r of q [R, nh 64] reads the n_keys rows of sentence
+    r // rows_per_sentence of kv [sentences * n_keys, 2 nh 64], sentences >= ceil(R / rows_per_sentence)."""
+    require_gpu(q, kv)
+    R, W, rps = q.shape[0], nh * 64, int(rows_per_sentence)
+    ldq, ldk = _gen_rows("beam_attn_cross", q, "q"), _gen_rows("beam_attn_cross", kv, "kv")
+    if rps < 1 or q.shape[1] != W or kv.shape[1] != 2 * W or kv.dtype != q.dtype or kv.shape[0] % n_keys \
+            or kv.shape[0] // n_keys < -(-R // rps):
+        raise KvqError(f"kvq.nnops.beam_attn_cross: q [R, {W}] needs kv [>= ceil(R / rows_per_sentence) * n_keys, {2 * W}] of its dtype, "
+                       f"got {tuple(kv.shape)}")
+    if out is None:
+        out = torch.empty((R, W), dtype=q.dtype, device=q.device)
+    check(lib().kvq_beam_attn(_gen_ptr(state), q.data_ptr(), ldq, None, None, 0, kv.data_ptr(), ldk, int(n_keys) * ldk, R, nh, 0, int(n_keys), 0,
+                              None, 0, rps, io_dtype_of(q), out.data_ptr(), _gen_rows("beam_attn_cross", out, "out"), stream_ptr()),
+          "kvq_beam_attn")
+    return out
+
+
+def _beam_rows(who, R, Lmax, **named):
+    for name, (x, dtype, shape) in named.items():
+        if x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous():
+            raise KvqError(f"kvq.nnops.{who}: {name} must be a contiguous {dtype} {shape} tensor")
+
+
+def beam_select(state, logits, V, W, ids, parent, scores, step_scores, anc, finished, lengths, step_logits=None):
+    """One step of beam search over logits [R, ld] in slot space (rows b W .. b W + W - 1 = sentence b): the W best of the live
+    beams' V continuations and the finished beams themselves become the new beams -- token, parent, score, end-token bookkeeping
+    and the extended ancestry rows (include/kvq.h).  t is read from the state; W = 1 .. 8."""
+    require_gpu(logits, ids, parent, scores, step_scores, anc, finished, lengths)
+    R = logits.shape[0]
+    ld = _gen_rows("beam_select", logits, "logits")
+    if ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_contiguous() or ids.shape[0] != R:
+        raise KvqError("kvq.nnops.beam_select: ids must be a contiguous int64 [R, Lmax] tensor")
+    Lmax = ids.shape[1]
+    if _beam_anc("beam_select", anc, R) != Lmax:
+        raise KvqError("kvq.nnops.beam_select: the ancestry table must be [2, R, Lmax]")
+    _beam_rows("beam_select", R, Lmax, parent=(parent, torch.int32, (R, Lmax)), step_scores=(step_scores, torch.float32, (R, Lmax)),
+               scores=(scores, torch.float32, (R,)), finished=(finished, torch.int32, (R,)), lengths=(lengths, torch.int32, (R,)))
+    if step_logits is not None:
+        _beam_rows("beam_select", R, Lmax, step_logits=(step_logits, torch.float32, (R, Lmax, V)))
+    if isinstance(W, bool) or not isinstance(W, int) or not 1 <= W <= BEAM_MAX:
+        raise KvqError(f"kvq.nnops.beam_select: W must be an int in 1 .. {BEAM_MAX}, got {W!r}")
+    check(lib().kvq_beam_select(_gen_ptr(state), logits.data_ptr(), ld, int(V), R, W, Lmax, io_dtype_of(logits), ids.data_ptr(),
+                                parent.data_ptr(), scores.data_ptr(), step_scores.data_ptr(), anc.data_ptr(), finished.data_ptr(),
+                                lengths.data_ptr(), _p(step_logits), stream_ptr()), "kvq_beam_select")
+
+
+def beam_gather(state, ids, anc, lengths, out=None):
+    """out [R, Lmax] int64 = the hypotheses of the beams now living in the rows: out[r, j] = ids[anc[t & 1][r, j], j] for
+    j < lengths[r], the state's pad id behind."""
+    require_gpu(ids, anc, lengths)
+    if ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_contiguous():
+        raise KvqError("kvq.nnops.beam_gather: ids must be a contiguous int64 [R, Lmax] tensor")
+    R, Lmax = ids.shape
+    if _beam_anc("beam_gather", anc, R) != Lmax:
+        raise KvqError("kvq.nnops.beam_gather: the ancestry table must be [2, R, Lmax]")
+    _beam_rows("beam_gather", R, Lmax, lengths=(lengths, torch.int32, (R,)))
+    if out is None:
+        out = torch.empty_like(ids)
+    elif out.dtype != torch.int64 or out.shape != ids.shape or not out.is_contiguous():
+        raise KvqError("kvq.nnops.beam_gather: out must be a contiguous int64 [R, Lmax] tensor")
+    check(lib().kvq_beam_gather(_gen_ptr(state), ids.data_ptr(), anc.data_ptr(), lengths.data_ptr(), R, Lmax, out.data_ptr(), stream_ptr()),
+          "kvq_beam_gather")
+    return out

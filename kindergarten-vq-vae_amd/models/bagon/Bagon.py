@@ -156,13 +156,17 @@ class Bagon(nn.Module):
         return engine_of(self).decode(latents, decoder_input_ids, decoder_attention_mask, target_ids=target_ids, quantize=quantize,
                                       want_logits=want_logits)
 
-    def generate_from_latents(self, latents, max_length, prompt_ids, **kw):
+    def generate_from_latents(self, latents, max_length, prompt_ids, num_beams=1, length_penalty=0.0, **kw):
         """TrainEngine.generate: free-running generation from latents [B, Se, H] -- the decoder sees the prompt [B, P] (e.g. a column
         of start ids) and what it has written itself, one token per position over a key/value cache: dict(ids [B, max_length],
         lengths, finished [, logits] [, indices]).  kw: eos_id, pad_id, temperature, seed, quantize, want_logits, graph.  Meaningful
-        for a model trained with DECODER_NEXT_TOKEN."""
+        for a model trained with DECODER_NEXT_TOKEN.  num_beams > 1: TrainEngine.beam_search instead (section 5j)
+        -- the same keys for the best hypothesis, and beam_ids, beam_scores, beam_lengths, beam_finished [B, num_beams, ...] best
+        first; kw: eos_id, pad_id, quantize, want_trace, graph."""
         from kvq.engine import engine_of
-        return engine_of(self).generate(latents, max_length, prompt_ids, **kw)
+        if num_beams == 1:
+            return engine_of(self).generate(latents, max_length, prompt_ids, **kw)
+        return engine_of(self).beam_search(latents, max_length, prompt_ids, num_beams, length_penalty=length_penalty, **kw)
 
     decoder_next_token_start_id = None     # DECODER_NEXT_TOKEN: main.py puts the start id here, the trainer's step shifts the decoder input by it
 

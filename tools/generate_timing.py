@@ -15,7 +15,14 @@ eager call under kvq._ffi.family_profile_begin() -- an event pair around every e
 the split of a step between the GEMMs, kvq_gen_attn and the rest.
 Prints one JSON document; profiles/generate.md records it.
 
+--num-beams W (> 1) measures TrainEngine.beam_search instead: beam_search on B sentences with W beams, graph
+and eager, against generate() on B W sentences in the same run -- the same row count through the same GEMMs, so the difference is
+what the selection over W V candidates and the reads through the ancestry table cost; tokens/s counts the B (max_length - 1)
+tokens of the best hypotheses.  Then the replay of either captured step alone, the census, and the family split of an eager
+beam call.  profiles/beam_search.md records it.
+
     PYTHONPATH=kindergarten-vq-vae_amd python3 tools/generate_timing.py [--out FILE.json] [--rounds 5] [--batch 256] [--se 32] [--max-length 32]
+                                                                         [--num-beams W]
 """
 import argparse
 import json
@@ -27,6 +34,51 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "kindergarten-vq-vae_amd")]
 
 
+def beam_timing(a, eng, lat, timed):
+    """beam_search on B sentences x W beams against generate() on B W sentences: the same rows, in alternating rounds"""
+    import torch
+
+    from kvq import _ffi
+    B, SE, L, W = a.batch, a.se, a.max_length, a.num_beams
+    prompt = torch.full((B, 1), 101, dtype=torch.int64, device="cuda")
+    lat_rows = lat.repeat_interleave(W, dim=0).contiguous()
+    prompt_rows = torch.full((B * W, 1), 101, dtype=torch.int64, device="cuda")
+    arms = {"beam_graph": lambda: eng.beam_search(lat, L, prompt, W),
+            "beam_eager": lambda: eng.beam_search(lat, L, prompt, W, graph=False),
+            "generate_same_rows": lambda: eng.generate(lat_rows, L, prompt_rows)}
+    res = {"model": a.model, "B": B, "num_beams": W, "rows": B * W, "Se": SE, "max_length": L, "rounds": a.rounds,
+           "device": torch.cuda.get_device_name(0)}
+    with torch.no_grad():
+        first = {k: fn() for k, fn in arms.items()}                       # warm-up of every arm (captures included)
+        res["graph_equals_eager"] = all(bool(torch.equal(first["beam_graph"][k], first["beam_eager"][k])) for k in ("beam_ids", "beam_scores"))
+        res["best_hypotheses_differing_from_greedy"] = int((first["beam_graph"]["ids"] != first["generate_same_rows"]["ids"][::W]).any(1).sum())
+        times = {k: [] for k in arms}
+        for _ in range(a.rounds):
+            for k, fn in arms.items():
+                times[k].append(timed(fn)[0])
+        for k, v in times.items():
+            ev, ho = sorted(t["event_s"] for t in v), sorted(t["host_s"] for t in v)
+            res[k] = dict(event_s_median=ev[len(ev) // 2], event_s_min=ev[0], event_s_max=ev[-1], host_s_median=ho[len(ho) // 2],
+                          sentence_tokens_per_s_median=B * (L - 1) / ev[len(ev) // 2], row_tokens_per_s_median=B * W * (L - 1) / ev[len(ev) // 2])
+        for name, entry in (("beam", next(iter(eng._beam_cache.values()))), ("generate_same_rows", next(iter(eng._gen_cache.values())))):
+            def replay_block(entry=entry):                                 # whole passes over the positions, t back to 0 in front of each
+                for _ in range(max(a.replays // (L - 1), 1)):
+                    entry["state"][0:1].zero_()
+                    for _ in range(L - 1):
+                        entry["graph"].replay()
+            dt, _ = timed(replay_block)
+            res[name + "_graph_replay_ms_per_step"] = 1e3 * dt["event_s"] / (max(a.replays // (L - 1), 1) * (L - 1))
+        res["census"] = eng.gen_census()
+        eng.beam_search(lat, L, prompt, W)                                 # leaves a valid state behind the replays
+        _ffi.family_profile_begin()
+        eng.beam_search(lat, L, prompt, W, graph=False)
+        ms, n, empty = _ffi.family_profile_end()
+        res["beam_eager_family_ms_per_call"] = ms
+        res["beam_eager_family_launches_per_call"] = n
+        res["empty_event_pair_ms"] = empty
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -36,6 +88,7 @@ def main():
     ap.add_argument("--max-length", type=int, default=32)
     ap.add_argument("--replays", type=int, default=310)
     ap.add_argument("--model", default="bert-base-uncased")
+    ap.add_argument("--num-beams", type=int, default=1)
     a = ap.parse_args()
     import torch
 
@@ -61,6 +114,16 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         return dict(host_s=time.perf_counter() - t0, event_s=e0.elapsed_time(e1) * 1e-3), out
+
+    if a.num_beams > 1:
+        res = beam_timing(a, eng, lat, timed)
+        text = json.dumps(res, indent=1)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text + "\n")
+        return
 
     def prefix_loop():
         ids = prompt
