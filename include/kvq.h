@@ -855,6 +855,43 @@ int kvq_gumbel_backward(const void* logits, const float* y_soft, const void* g_y
  *                     else ids[b, t+1] = choice and, if choice == eos_id, finished[b] = 1 and lengths[b] = t + 2.
  *                   step_logits (may be NULL) [B, Lmax, V] f32: row (b, t) receives the logits of columns < V.
  *                 ld %% 8 == 0, 16-byte aligned logits.
+ * kvq_gen_select_filtered  kvq_gen_select on a top-k / top-p filtered distribution, with the score of what it chose (DESIGN.md
+ *                 section 5k).  Filter state, on the device beside the generation state: 16 bytes, 4-byte aligned,
+ *                     struct { int32 top_k; float top_p; int32 reserved[2]; }
+ *                   reserved = 0; a non-zero reserved word makes the kernel store nothing.  The filters are read from there, never
+ *                   from a launch argument: one captured step serves every (top_k, top_p, temperature, seed).
+ *                   y_v = fl32(logit_v * inv_tau) for v < V, the product of kvq_gen_select (inv_tau = 1 and g = 0 in a greedy state).
+ *                   A NaN is never kept and never counted (n_valid = the others); a -inf has mass 0.
+ *                   ORDER: v before w iff y_v > y_w, or y_v == y_w and v < w.  Every kept set is a prefix of the order.
+ *                   top-k (top_k >= 1): K = the first min(top_k, n_valid) of the order; top_k <= 0: K = every valid column.
+ *                   top-p (0 < top_p < 1; anything else, a NaN included, turns it off), inside K as HuggingFace chains its warpers:
+ *                     m = max y, e_v = exp(y_v - m), Z = sum over K of e, C_j = the mass of the first j of the order;
+ *                     n_keep = the smallest j >= 1 with C_j >= fl(top_p Z) -- the token that crosses p is kept
+ *                     (TopPLogitsWarper) -- and |K| if no j reaches it in the kernel's arithmetic.
+ *                   choice = the first arg-max over the kept set of (y_v + g_v), g_v EXACTLY kvq_gen_select's noise (same Philox
+ *                     counters, key and u -> g): filters off, the bits of kvq_gen_select; filters on, kvq_gen_select on the logits
+ *                     with every column outside the kept set at -inf.  An exact draw from the distribution renormalised over the set.
+ *                   A greedy state ignores the filters (the arg-max is in every kept set): n_keep = n_valid.  A row with no valid
+ *                   logit chooses 0 with n_keep = 0.  Prompt / finished / end-token bookkeeping and step_logits: kvq_gen_select's.
+ *                   step_kept, step_cut [B, Lmax] int32, step_logprob [B, Lmax] f32 (each may be NULL): row (b, t) receives n_keep,
+ *                     the id of the last kept element of the order (-1 when n_keep = 0) and
+ *                     log p~(choice) = fl(fl(y_c - m) - log C_n_keep), p~ = the distribution that was sampled from (NaN when n_keep = 0).
+ *                   One workgroup of 1024 threads a sentence, the row read once (16 bytes a lane) and held in registers:
+ *                   V <= 32768, refused above.  The cut is a selection, not a sort: y maps to an order-preserving 32-bit key and the
+ *                   key of the last kept element is found bit by bit, one block reduction (count and mass of the keys continuing
+ *                   the decided prefix with a 1) a bit; the group tied at the cut shares one mass e_T, so the j of it to keep follow
+ *                   from the count / mass left, and the cut is its j-th lowest index (a 16-bit selection of the same kind).
+ *                   No atomics, fixed summation orders: the same inputs give the same bits, eagerly and under graph replay.
+ *                   ROUNDING.  A mass is summed as: 8 columns of a thread as a tree (3 roundings), its 4 chunks in order (3), the
+ *                   wave as a butterfly (6), the 16 waves as a tree (4) = 16; C_j adds at most 32 such sums in the order of the
+ *                   rounds (32) and j e_T (2): 50 roundings, each at most 2^-24 of a partial sum <= Z.  A term e_v carries the
+ *                   rounding of y_v - m (2^-24 |y_v - m| relative; summed with weights e_v / Z that is at most 2^-24 log V <= 10.4
+ *                   2^-24, the entropy bound) and expf's 1 ulp (2 2^-24).  So |C_j - exact| <= 62.4 2^-24 Z, the same for Z, one
+ *                   more rounding for top_p Z: the comparison C_j >= top_p Z is decided as an exact one at some p' with
+ *                       |p' - top_p| <= TOL_MASS = 2^-17     (>= (2 * 62.4 + 1) 2^-24)
+ *                   and  |step_logprob - exact| <= 2^-17 + 2^-22 (|y_c - m| + |log C|)   (log C: C's relative error 62.4 2^-24 <
+ *                   2^-18 by the same count relative to C >= 1, logf's ulp and two subtractions on top).  tests/_sample_ref.py.
+ *                 ld %% 8 == 0, 16-byte aligned logits.
  * kvq_gen_advance one thread: t += 1.  A launch of its own, so that no kernel of a step races with the increment. */
 int kvq_gen_embed(const void* state, const int64_t* ids, const void* word, const void* pos, const void* type_row, const float* gamma,
                   const float* beta, int B, int H, int64_t V, int pos_rows, float eps, int io_dtype, void* out, void* stream);
@@ -863,6 +900,9 @@ int kvq_gen_attn(const void* state, const void* q, int64_t ldq, const void* k_ne
                  int64_t ldo, void* stream);
 int kvq_gen_select(const void* state, const void* logits, int64_t ld, int V, int B, int io_dtype, int64_t* ids, int32_t* finished,
                    int32_t* lengths, float* step_logits, void* stream);
+int kvq_gen_select_filtered(const void* state, const void* filter, const void* logits, int64_t ld, int V, int B, int io_dtype, int64_t* ids,
+                            int32_t* finished, int32_t* lengths, float* step_logits, int32_t* step_kept, int32_t* step_cut,
+                            float* step_logprob, void* stream);
 int kvq_gen_gumbel_debug(const uint32_t* bits, int64_t n, float* out, void* stream);
 int kvq_gen_advance(void* state, void* stream);
 

@@ -65,6 +65,11 @@ CKPT_PATH = None                     # "<RUN_DIR>/bagon_ckpt_loss_recon_val_best
 RESULTS_DIR = None                   # default: <RUN_DIR>
 FREE_RUNNING = False                 # True (or --free-running on the command line): the plain and the edited latent are GENERATED from each sentence's first token (model.generate_from_latents) instead of decoded against the sentence's own ids; for a model trained with DECODER_NEXT_TOKEN
 NUM_BEAMS = 1                        # N > 1 (or --num-beams N on the command line; with free running): the plain and the edited sentence are the best of N hypotheses of beam search (model.generate_from_latents(num_beams=N)); the table gains recon_ / edited_ score, runner_up_<i> and runner_up_<i>_score columns
+SAMPLES = 0                          # N > 0 (or --samples N; free-running generation, one beam): every latent is generated N more times, sampled with seeds SEED .. SEED + N - 1 (model.generate_from_latents(temperature, top_k, top_p, seed, want_scores=True)); the table gains sample_<i> / sample_<i>_score (and edited_sample_<i> / edited_sample_<i>_score) columns
+TEMPERATURE = 1.0                    # --temperature T: of the samples
+TOP_K = 0                            # --top-k K: the samples draw from the K most probable tokens (0 = off)
+TOP_P = 1.0                          # --top-p P: ... from the shortest prefix of them whose mass reaches P (1 = off)
+SEED = 0                             # --seed S: the first sample's seed
 
 for _k in [k for k in list(globals()) if k.isupper()]:
     _v = os.environ.get("KVQ_" + _k)
@@ -112,8 +117,28 @@ def num_beams_switch(default):
     return int(argv[argv.index("--num-beams") + 1]) if "--num-beams" in argv else int(default)
 
 
+def sampling_switch(samples, temperature, top_k, top_p, seed, num_beams=1):
+    """--samples N --temperature T --top-k K --top-p P --seed S on the command line, else the configured constants:
+    dict(samples, temperature, top_k, top_p, seed).  Samples are drawn, not searched: refused together with num_beams > 1.
+    A sample is always generated free-running (there is nothing to draw in a teacher-forced decode)."""
+    argv = sys.argv[1:]
+    opt = lambda flag, default, kind: kind(argv[argv.index(flag) + 1]) if flag in argv else kind(default)
+    s = dict(samples=opt("--samples", samples, int), temperature=opt("--temperature", temperature, float), top_k=opt("--top-k", top_k, int),
+             top_p=opt("--top-p", top_p, float), seed=opt("--seed", seed, int))
+    if s["samples"] < 0:
+        raise SystemExit(f"--samples must be >= 0, got {s['samples']}")
+    if s["samples"] and num_beams > 1:
+        raise SystemExit(f"--samples {s['samples']} together with --num-beams {num_beams}: samples are drawn with one beam (sampled beams are not supported)")
+    return s
+
+
+def sample_columns(tokenizer, i, ids, score, prefix=""):
+    """one sample of one sentence as table columns, as beam_columns adds the runner-ups"""
+    return {f"{prefix}sample_{i}": tokenizer.batch_decode(ids.unsqueeze(0).cpu())[0], f"{prefix}sample_{i}_score": float(score)}
+
+
 def latent_arithmetics(model, tokenizer, s_neg, s_aff, s_edit, device, seq_len, batch_size, add_special_tokens=False, alpha=1.0,
-                       free_running=False, num_beams=1):
+                       free_running=False, num_beams=1, sampling=None):
     """-> (LatentCensus over group 0 = s_aff, group 1 = s_neg; rows of original / reconstructed / edited sentences of s_edit)"""
     H = model.encoder.config.hidden_size
     quantize = hasattr(model, "vector_quantizer")
@@ -141,11 +166,21 @@ def latent_arithmetics(model, tokenizer, s_neg, s_aff, s_edit, device, seq_len, 
                 i = len(rows) - 1 - first
                 rows[-1].update(beam_columns(tokenizer, plain_out["beam_ids"][i], plain_out["beam_scores"][i], "recon_"))
                 rows[-1].update(beam_columns(tokenizer, edited_out["beam_ids"][i], edited_out["beam_scores"][i], "edited_"))
+        if sampling and sampling["samples"]:    # the same captured step every time: the seed lives in the state
+            start = ids[:, :1].contiguous()
+            for prefix, lat in (("", z), ("edited_", census.shift(z, 1, 0, alpha=alpha))):
+                for n in range(sampling["samples"]):
+                    out = model.generate_from_latents(lat, seq_len, start, quantize=quantize, temperature=sampling["temperature"],
+                                                      top_k=sampling["top_k"], top_p=sampling["top_p"], seed=sampling["seed"] + n, want_scores=True)
+                    for i in range(len(batch)):
+                        rows[first + i].update(sample_columns(tokenizer, n, out["ids"][i], out["scores"][i], prefix))
     return census, rows
 
 
 def main():
     import pandas as pd
+    free_running, num_beams = bool(FREE_RUNNING) or "--free-running" in sys.argv[1:], num_beams_switch(NUM_BEAMS)
+    sampling = sampling_switch(SAMPLES, TEMPERATURE, TOP_K, TOP_P, SEED, num_beams)
     if not torch.cuda.is_available():
         raise SystemExit("the analysis needs an MI355X: the encoder, decoder and latent kernels have no CPU fallback")
     device = torch.device("cuda", 0)
@@ -179,8 +214,7 @@ def main():
     torch.set_grad_enabled(False)                                                            # :45
     tokenizer = load_tokenizer(TOKENIZER_NAME)
     census, rows = latent_arithmetics(model, tokenizer, s_neg, s_aff, s_edit, device, TOKENIZED_SENTENCE_MAX_LENGTH, BATCH_SIZE,
-                                      TOKENIZER_ADD_SPECIAL_TOKENS, ALPHA, free_running=bool(FREE_RUNNING) or "--free-running" in sys.argv[1:],
-                                      num_beams=num_beams_switch(NUM_BEAMS))
+                                      TOKENIZER_ADD_SPECIAL_TOKENS, ALPHA, free_running=free_running, num_beams=num_beams, sampling=sampling)
     results_dir = RESULTS_DIR or run_dir
     os.makedirs(results_dir, exist_ok=True)
     written = write_table(pd.DataFrame(rows), f"{results_dir}/latent_arithmetics.feather")

@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))      # package root 
 import torch  # noqa: E402
 
 from analyses.get_max_acc_sentences import read_table, write_table  # noqa: E402
-from analyses.latent_arithmetics.latent_arithmetics import beam_columns, corpus_table, num_beams_switch  # noqa: E402
+from analyses.latent_arithmetics.latent_arithmetics import beam_columns, corpus_table, num_beams_switch, sample_columns, sampling_switch  # noqa: E402
 from common.consts import *  # noqa: E402,F401,F403
 from kvq.tokenizer import load_tokenizer  # noqa: E402
 from models.shelgon3.MultiVectorQuantizer import MultiVectorQuantizer  # noqa: E402
@@ -60,6 +60,11 @@ CKPT_PATH = None                     # "<RUN_DIR>/Shelgon_ckpt_loss_recon_val_be
 RESULTS_DIR = None                   # default: <RUN_DIR>
 FREE_RUNNING = False                 # True (or --free-running on the command line): the K variants are GENERATED from the sentence's first token (model.traverse_codes(free_running=True)) instead of decoded against the sentence's own ids; for a model trained with DECODER_NEXT_TOKEN
 NUM_BEAMS = 1                        # N > 1 (or --num-beams N on the command line; with free running): every variant is the best of N hypotheses of beam search (model.traverse_codes(num_beams=N)); the table gains score, runner_up_<i> and runner_up_<i>_score columns
+SAMPLES = 0                          # N > 0 (or --samples N; free-running generation, one beam): every variant is generated N more times, sampled with seeds SEED .. SEED + N - 1 (model.traverse_codes(temperature, top_k, top_p, seed, want_scores=True)); the table gains sample_<i> and sample_<i>_score columns
+TEMPERATURE = 1.0                    # --temperature T: of the samples
+TOP_K = 0                            # --top-k K: the samples draw from the K most probable tokens (0 = off)
+TOP_P = 1.0                          # --top-p P: ... from the shortest prefix of them whose mass reaches P (1 = off)
+SEED = 0                             # --seed S: the first sample's seed
 
 for _k in [k for k in list(globals()) if k.isupper()]:
     _v = os.environ.get("KVQ_" + _k)
@@ -71,9 +76,10 @@ for _k in [k for k in list(globals()) if k.isupper()]:
 
 
 def code_traversal(model, tokenizer, sentences, device, seq_len, positions=None, factor=0, add_special_tokens=False, free_running=False,
-                   num_beams=1):
+                   num_beams=1, sampling=None):
     """Rows of the result table for every (sentence, position, code).  free_running: the variants are generated, not teacher-forced;
-    num_beams > 1: by beam search, the runner-up hypotheses and the scores (sums of log-probabilities) in columns of their own."""
+    num_beams > 1: by beam search, the runner-up hypotheses and the scores (sums of log-probabilities) in columns of their own;
+    sampling (sampling_switch): samples of every variant and their scores in columns of their own."""
     t = tokenizer(list(sentences), return_tensors="pt", padding="max_length", max_length=seq_len, add_special_tokens=add_special_tokens)
     ids, mask = t.input_ids.to(device), t.attention_mask.to(device)                          # :98-108
     lengths = t.attention_mask.sum(1).tolist()
@@ -88,11 +94,20 @@ def code_traversal(model, tokenizer, sentences, device, seq_len, positions=None,
                              "recon_sentence": r, "n_changed_tokens": int(c)})
                 if "beam_ids" in out:
                     rows[-1].update(beam_columns(tokenizer, out["beam_ids"][k], out["beam_scores"][k]))
+            if sampling and sampling["samples"]:  # the same captured step every time: the seed lives in the state
+                first = len(rows) - len(decoded)
+                for n in range(sampling["samples"]):
+                    smp = model.traverse_codes(ids, mask, b, int(pos), factor=factor, free_running=True, temperature=sampling["temperature"],
+                                               top_k=sampling["top_k"], top_p=sampling["top_p"], seed=sampling["seed"] + n, want_scores=True)
+                    for k in range(len(decoded)):
+                        rows[first + k].update(sample_columns(tokenizer, n, smp["recon_ids"][k], smp["scores"][k]))
     return rows
 
 
 def main():
     import pandas as pd
+    free_running, num_beams = bool(FREE_RUNNING) or "--free-running" in sys.argv[1:], num_beams_switch(NUM_BEAMS)
+    sampling = sampling_switch(SAMPLES, TEMPERATURE, TOP_K, TOP_P, SEED, num_beams)
     if not torch.cuda.is_available():
         raise SystemExit("the analysis needs an MI355X: the encoder, quantiser and decoder kernels have no CPU fallback")
     device = torch.device("cuda", 0)
@@ -122,8 +137,7 @@ def main():
     torch.set_grad_enabled(False)                                                            # :42
     tokenizer = load_tokenizer(TOKENIZER_NAME)
     rows = code_traversal(model, tokenizer, all_gen_fact, device, TOKENIZED_SENTENCE_MAX_LENGTH, POSITIONS, FACTOR_INDEX,
-                          TOKENIZER_ADD_SPECIAL_TOKENS, free_running=bool(FREE_RUNNING) or "--free-running" in sys.argv[1:],
-                          num_beams=num_beams_switch(NUM_BEAMS))
+                          TOKENIZER_ADD_SPECIAL_TOKENS, free_running=free_running, num_beams=num_beams, sampling=sampling)
     results_dir = RESULTS_DIR or run_dir
     os.makedirs(results_dir, exist_ok=True)
     written = write_table(pd.DataFrame(rows), f"{results_dir}/code_traversal.feather")

@@ -1,11 +1,12 @@
 // kvq_generate.hip -- free-running generation: one decoder token per sentence and launch, over a key/value cache (gfx950).
 //
-// TrainEngine.generate runs the decoder one position at a time: [B, H] rows through the GEMMs the training step uses, and the four
+// TrainEngine.generate runs the decoder one position at a time: [B, H] rows through the GEMMs the training step uses, and the
 // kernels of this file for what is not a GEMM or a LayerNorm:
 //     kvq_gen_embed     BertEmbeddings of the token at column t of `ids` (the bits of kvq_embed_ln_fwd's row for it)
 //     kvq_gen_attn      one query row per (sentence, head) against the cache (self-attention: this step's k | v rows are appended
 //                       first) or against the projected latent (cross-attention)
 //     kvq_gen_select    the next token: arg-max of logit / tau + Gumbel noise (none when greedy), prompt / end-token bookkeeping
+//     kvq_gen_select_filtered   the same from a top-k / top-p filtered distribution, with the score of the choice (filter state)
 //     kvq_gen_advance   one thread: t += 1
 // Every kernel reads the position t from the 32-byte generation state on the device (include/kvq.h), so one captured chain of
 // launches serves every position.  No atomics, fixed summation orders: the same inputs give the same bits.
@@ -349,6 +350,340 @@ __global__ __launch_bounds__(SEL_THREADS) void gen_select_kernel(const GenState*
                 if (choice == st->eos_id) { finished[b] = 1; lengths[b] = t + 2; }
             }
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// next token from a top-k / top-p filtered distribution (include/kvq.h "kvq_gen_select_filtered"): one workgroup of 1024 threads
+// per sentence, the row read ONCE, 16 bytes a lane, and kept in registers (FLT_CHUNKS chunks of 8 columns a thread: V <= 32768).
+//
+// The kept set is a prefix of the order (y descending, then the index ascending), so it is known by its LAST element: a threshold
+// value and, inside the group tied at it, an index.  Both are selections, found bit by bit: y maps to an order-preserving 32-bit
+// key (0 = a NaN or a column >= V), and a round asks "does the cut lie among the keys that continue the decided prefix with a 1?"
+// from ONE block reduction of their count (top-k) and of their mass (top-p) -- rank and mass above a threshold are both monotone
+// in it.  Members of the tied group share one mass, so the number of them to keep follows from the count or the mass that is left,
+// and the index of the last of them is a second, 16-bit, selection.  top-k before top-p: the first search gives Z of the top k.
+//
+// Summation order of every mass (the premise of TOL_MASS, include/kvq.h): a thread adds its chunk of 8 as a tree (3 roundings),
+// its chunks in ascending order (3), the wave is a butterfly (6), the 16 waves a tree (4): 16 roundings; the mass above the
+// threshold is the sum of at most 32 such round sums in the order of the rounds (32), then + j e_T (2).  Every thread forms the
+// same sums from the same LDS words, so every decision is uniform; no atomics.
+// ---------------------------------------------------------------------------------------------------------------
+struct GenFilter {
+    int32_t top_k;                  // <= 0: off
+    float top_p;                    // outside (0, 1): off
+    int32_t reserved[2];            // 0; anything else: the kernel stores nothing
+};
+static_assert(sizeof(GenFilter) == 16, "the filter state is 16 bytes (include/kvq.h)");
+
+constexpr int FLT_THREADS = 1024;
+constexpr int FLT_WAVES = FLT_THREADS / WAVE;
+constexpr int FLT_CHUNKS = 4;
+constexpr int FLT_N = FLT_CHUNKS * 8;                       // columns a thread holds
+constexpr int FLT_MAX_V = FLT_THREADS * FLT_N;              // 32768
+static_assert(FLT_WAVES == 16, "the wave tree of flt_reduce is written for 16 waves");
+
+// y -> key: larger y, larger key; -0 counts as +0 (they compare equal); a NaN -> 0, below every value (-inf -> 0x007fffff)
+__device__ __forceinline__ unsigned flt_key(float y) {
+    if (y != y) return 0u;
+    const unsigned u = __float_as_uint(y == 0.f ? 0.f : y);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float flt_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+struct FltShared {
+    int c[2][FLT_WAVES];            // two slots, used in turn: one barrier a reduction
+    float m[2][FLT_WAVES];
+    float av[FLT_WAVES], ay[FLT_WAVES];
+    int ai[FLT_WAVES];
+};
+
+__device__ __forceinline__ float flt_tree8(const float (&a)[8]) { return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7])); }
+
+// (c, m) of the thread -> of the workgroup, the same bits in every thread.  MODE 0: c only; 1: c and the sum of m; 2: c and the max of m
+template <int MODE>
+__device__ __forceinline__ void flt_reduce(int& c, float& m, FltShared& sh, int& slot, int lane, int wave) {
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        c += __shfl_xor(c, k, WAVE);
+        if (MODE == 1) m += __shfl_xor(m, k, WAVE);
+        if (MODE == 2) m = fmaxf(m, __shfl_xor(m, k, WAVE));
+    }
+    if (lane == 0) {
+        sh.c[slot][wave] = c;
+        if (MODE != 0) sh.m[slot][wave] = m;
+    }
+    __syncthreads();
+    int cc[FLT_WAVES];
+    float mm[FLT_WAVES];
+#pragma unroll
+    for (int w = 0; w < FLT_WAVES; ++w) {
+        cc[w] = sh.c[slot][w];
+        mm[w] = MODE != 0 ? sh.m[slot][w] : 0.f;
+    }
+#pragma unroll
+    for (int s = 1; s < FLT_WAVES; s <<= 1)
+#pragma unroll
+        for (int w = 0; w < FLT_WAVES; w += 2 * s) {
+            cc[w] += cc[w + s];
+            if (MODE == 1) mm[w] += mm[w + s];
+            if (MODE == 2) mm[w] = fmaxf(mm[w], mm[w + s]);
+        }
+    c = cc[0];
+    m = mm[0];
+    slot ^= 1;
+}
+
+// The last element of the order by `key` (descending) that is kept: T = its key, cnt_gt / mass_gt = count and mass of the keys
+// above T.  Kept is what comes before the count reaches kk (1 <= kk <= the keys that are not 0) or, with MASS, before the mass
+// reaches `target`, whichever is first.  Bits top_bit .. 0, the key's upper bits are 0.  kk comes back lowered to the end of the
+// last half the search entered, so that ca < kk <= ca + (keys left) holds in every round and T is the key of an element.
+template <bool MASS>
+__device__ __forceinline__ void flt_search(const unsigned (&key)[FLT_N], const float (&e)[FLT_N], int top_bit, int& kk, float target,
+                                           FltShared& sh, int& slot, int lane, int wave, unsigned& T, int& cnt_gt, float& mass_gt) {
+    unsigned prefix = 0;
+    int ca = 0;
+    float ma = 0.f;
+    for (int bit = top_bit; bit >= 0; --bit) {
+        const unsigned cand = (prefix >> bit) | 1u;            // the upper half of what is left: bits 31 .. bit equal to cand
+        int c = 0;
+        float m = 0.f;
+#pragma unroll
+        for (int u = 0; u < FLT_CHUNKS; ++u) {
+            float a[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const bool hit = (key[8 * u + i] >> bit) == cand;
+                c += hit ? 1 : 0;
+                a[i] = MASS && hit ? e[8 * u + i] : 0.f;
+            }
+            if (MASS) m += flt_tree8(a);
+        }
+        flt_reduce<MASS ? 1 : 0>(c, m, sh, slot, lane, wave);
+        const bool up = ca + c >= kk || (MASS && c > 0 && ma + m >= target);
+        if (up) {
+            prefix |= 1u << bit;
+            kk = min(kk, ca + c);                              // the cut lies in this half at the latest at its end -- also when the mass,
+        } else {                                               // summed again in finer pieces, falls short of the target by a rounding
+            ca += c;
+            if (MASS) ma = ma + m;
+        }
+    }
+    T = prefix;
+    cnt_gt = ca;
+    mass_gt = ma;
+}
+
+// The cut in full: T as flt_search, j = how many of the ntie keys equal to T are kept (by index order), n_keep = cnt_gt + j,
+// C = mass_gt + j e_T, the mass of the kept set.
+template <bool MASS>
+__device__ __forceinline__ void flt_cut(const unsigned (&key)[FLT_N], const float (&e)[FLT_N], int kk, float target, float mx, FltShared& sh,
+                                        int& slot, int lane, int wave, unsigned& T, int& j, int& n_keep, float& C) {
+    int cg;
+    float mg;
+    flt_search<MASS>(key, e, 31, kk, target, sh, slot, lane, wave, T, cg, mg);
+    int ntie = 0;
+    float above = 0.f;
+#pragma unroll
+    for (int u = 0; u < FLT_CHUNKS; ++u) {
+        float a[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            ntie += key[8 * u + i] == T ? 1 : 0;
+            a[i] = !MASS && key[8 * u + i] > T ? e[8 * u + i] : 0.f;
+        }
+        if (!MASS) above += flt_tree8(a);
+    }
+    flt_reduce<1>(ntie, above, sh, slot, lane, wave);
+    if (!MASS) mg = above;
+    const float eT = expf(flt_unkey(T) - mx);                  // the bits every member of the group holds
+    const int jk = min(kk - cg, ntie);
+    int jp = ntie;
+    if (MASS) {                                                // the smallest j in 1 .. ntie with mass_gt + j e_T >= target, else ntie
+        int lo = 1, hi = ntie;
+        if (mg + (float)hi * eT >= target) {
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (mg + (float)mid * eT >= target) hi = mid;
+                else lo = mid + 1;
+            }
+            jp = lo;
+        }
+    }
+    j = min(jk, jp);
+    n_keep = cg + j;
+    C = mg + (float)j * eT;
+}
+
+template <int DT>
+__global__ __launch_bounds__(FLT_THREADS) void gen_select_filtered_kernel(const GenState* __restrict__ st, const GenFilter* __restrict__ fs,
+                                                                           const void* __restrict__ logits, int64_t ld, int V,
+                                                                           int64_t* __restrict__ ids, int32_t* __restrict__ finished,
+                                                                           int32_t* __restrict__ lengths, float* __restrict__ step_logits,
+                                                                           int32_t* __restrict__ step_kept, int32_t* __restrict__ step_cut,
+                                                                           float* __restrict__ step_logprob) {
+    __shared__ FltShared sh;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t = st->t, Lmax = st->Lmax;
+    if (t < 0 || t >= Lmax) return;                            // (uniform)
+    if (fs->reserved[0] != 0 || fs->reserved[1] != 0) return;  // (uniform) a filter state this kernel does not know
+    const bool sample = st->inv_tau > 0.f;                     // (uniform)
+    const float inv_tau = sample ? st->inv_tau : 1.0f;
+    const unsigned k0 = st->seed_lo, k1 = st->seed_hi;
+    const int top_k = fs->top_k;
+    const float top_p = fs->top_p;
+    float* lrow = step_logits ? step_logits + ((size_t)b * Lmax + t) * V : nullptr;
+    const size_t at = (size_t)b * Lmax + t;
+    int slot = 0;
+
+    // ---- the row: keys, the count of valid columns, the maximum ----
+    unsigned key[FLT_N];
+    float e[FLT_N];                                            // y first, exp(y - max) then
+    const int nchunk = (V + 7) >> 3;                           // (ld % 8 == 0: the chunk lies inside the row)
+    int nv = 0;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < FLT_CHUNKS; ++u) {
+        const int c = tid + FLT_THREADS * u;
+        if (c < nchunk) {
+            const f32x8 x8 = IO<DT>::load8(logits, (size_t)b * ld + 8 * c);
+            const float x[8] = {x8.lo.x, x8.lo.y, x8.lo.z, x8.lo.w, x8.hi.x, x8.hi.y, x8.hi.z, x8.hi.w};
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int v = 8 * c + i;
+                unsigned k = 0u;
+                float y = 0.f;
+                if (v < V) {
+                    if (lrow) lrow[v] = x[i];
+                    y = x[i] * inv_tau;
+                    k = flt_key(y);
+                }
+                key[8 * u + i] = k;
+                e[8 * u + i] = y;
+                if (k != 0u) { nv += 1; mx = fmaxf(mx, y); }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { key[8 * u + i] = 0u; e[8 * u + i] = 0.f; }
+        }
+    }
+    flt_reduce<2>(nv, mx, sh, slot, lane, wave);
+
+    bool store = false;                                        // (uniform) whether column t + 1 takes the choice
+    if (t + 1 < Lmax && t + 1 >= st->P) store = true;
+    if (nv == 0) {                                             // (uniform) a row with no valid logit: 0, as kvq_gen_select
+        if (tid == 0) {
+            if (store) {
+                int64_t* dst = ids + (size_t)b * Lmax + t + 1;
+                if (finished[b]) {
+                    *dst = st->pad_id;
+                } else {
+                    *dst = 0;
+                    if (0 == st->eos_id) { finished[b] = 1; lengths[b] = t + 2; }
+                }
+            }
+            if (step_kept) step_kept[at] = 0;
+            if (step_cut) step_cut[at] = -1;
+            if (step_logprob) step_logprob[at] = __builtin_nanf("");
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < FLT_N; ++i) e[i] = key[i] != 0u ? expf(e[i] - mx) : 0.f;
+
+    // ---- the cut ----
+    const bool need_k = sample && top_k >= 1 && top_k < nv;    // (uniform; a greedy state ignores the filters)
+    const bool need_p = sample && top_p > 0.f && top_p < 1.f;
+    const int kk = need_k ? top_k : nv;
+    unsigned T;
+    int j, n_keep;
+    float C;
+    if (need_p) {
+        float Z;
+        if (need_k) {                                          // Z of the first kk of the order
+            flt_cut<false>(key, e, kk, INFINITY, mx, sh, slot, lane, wave, T, j, n_keep, Z);
+        } else {
+            int none = 0;
+            Z = 0.f;
+#pragma unroll
+            for (int u = 0; u < FLT_CHUNKS; ++u) {
+                const float a[8] = {e[8 * u], e[8 * u + 1], e[8 * u + 2], e[8 * u + 3], e[8 * u + 4], e[8 * u + 5], e[8 * u + 6], e[8 * u + 7]};
+                Z += flt_tree8(a);
+            }
+            flt_reduce<1>(none, Z, sh, slot, lane, wave);
+        }
+        flt_cut<true>(key, e, kk, top_p * Z, mx, sh, slot, lane, wave, T, j, n_keep, C);
+    } else {
+        flt_cut<false>(key, e, kk, INFINITY, mx, sh, slot, lane, wave, T, j, n_keep, C);
+    }
+
+    // ---- the index of the j-th (by index) of the group tied at T ----
+    unsigned k2[FLT_N];
+#pragma unroll
+    for (int u = 0; u < FLT_CHUNKS; ++u)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) k2[8 * u + i] = key[8 * u + i] == T ? (unsigned)(FLT_MAX_V - (8 * (tid + FLT_THREADS * u) + i)) : 0u;
+    unsigned T2;
+    int cg2;
+    float mg2;
+    int j2 = j;
+    flt_search<false>(k2, e, 15, j2, INFINITY, sh, slot, lane, wave, T2, cg2, mg2);
+    const int cut = FLT_MAX_V - (int)T2;
+
+    // ---- the choice: first arg-max of y + g over the kept set, g as kvq_gen_select draws it ----
+    float bv = -INFINITY, by = 0.f;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int u = 0; u < FLT_CHUNKS; ++u) {
+        const int c = tid + FLT_THREADS * u;
+        bool kept[8], any = false;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            kept[i] = key[8 * u + i] > T || (key[8 * u + i] == T && 8 * c + i <= cut);
+            any |= kept[i];
+        }
+        if (any) {
+            float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            if (sample) {                                      // (uniform)
+                const U4 r0 = philox4x32((unsigned)(2 * c), (unsigned)b, (unsigned)t, 0x47454e53u, k0, k1);
+                const U4 r1 = philox4x32((unsigned)(2 * c + 1), (unsigned)b, (unsigned)t, 0x47454e53u, k0, k1);
+                g[0] = gen_gumbel_from_bits(r0.x); g[1] = gen_gumbel_from_bits(r0.y); g[2] = gen_gumbel_from_bits(r0.z); g[3] = gen_gumbel_from_bits(r0.w);
+                g[4] = gen_gumbel_from_bits(r1.x); g[5] = gen_gumbel_from_bits(r1.y); g[6] = gen_gumbel_from_bits(r1.z); g[7] = gen_gumbel_from_bits(r1.w);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (kept[i]) {
+                    const float y = flt_unkey(key[8 * u + i]);
+                    const float s = y + g[i];
+                    if (sel_better(s, 8 * c + i, bv, bi)) { bv = s; bi = 8 * c + i; by = y; }
+                }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ov = __shfl_xor(bv, m, WAVE), oy = __shfl_xor(by, m, WAVE);
+        const int oi = __shfl_xor(bi, m, WAVE);
+        if (sel_better(ov, oi, bv, bi)) { bv = ov; bi = oi; by = oy; }
+    }
+    if (lane == 0) { sh.av[wave] = bv; sh.ai[wave] = bi; sh.ay[wave] = by; }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < FLT_WAVES; ++w)
+            if (sel_better(sh.av[w], sh.ai[w], bv, bi)) { bv = sh.av[w]; bi = sh.ai[w]; by = sh.ay[w]; }
+        const int choice = bi == 0x7fffffff ? 0 : bi;
+        if (store) {
+            int64_t* dst = ids + (size_t)b * Lmax + t + 1;
+            if (finished[b]) {
+                *dst = st->pad_id;
+            } else {
+                *dst = choice;
+                if (choice == st->eos_id) { finished[b] = 1; lengths[b] = t + 2; }
+            }
+        }
+        if (step_kept) step_kept[at] = n_keep;
+        if (step_cut) step_cut[at] = cut;
+        if (step_logprob) step_logprob[at] = bi == 0x7fffffff ? __builtin_nanf("") : (by - mx) - logf(C);
     }
 }
 
@@ -700,6 +1035,30 @@ int kvq_gen_select(const void* state, const void* logits, int64_t ld, int V, int
         hipLaunchKernelGGL(gen_select_kernel<KVQ_BF16>, dim3((unsigned)B), dim3(SEL_THREADS), 0, s, gs, logits, ld, V, ids, finished, lengths,
                            step_logits);
     return check_launch("gen_select_kernel");
+}
+
+int kvq_gen_select_filtered(const void* state, const void* filter, const void* logits, int64_t ld, int V, int B, int io_dtype, int64_t* ids,
+                            int32_t* finished, int32_t* lengths, float* step_logits, int32_t* step_kept, int32_t* step_cut,
+                            float* step_logprob, void* stream) {
+    KVQ_REQUIRE(state && filter && logits && ids && finished && lengths, "kvq_gen_select_filtered: null pointer argument");
+    KVQ_REQUIRE(io_dtype == KVQ_F32 || io_dtype == KVQ_BF16, "kvq_gen_select_filtered: unsupported io dtype %d", io_dtype);
+    KVQ_REQUIRE(B > 0 && V > 0 && ld >= V, "kvq_gen_select_filtered: B, V must be positive and ld >= V (B=%d V=%d ld=%lld)", B, V, (long long)ld);
+    KVQ_REQUIRE(V <= FLT_MAX_V, "kvq_gen_select_filtered: V=%d above the %d columns a workgroup holds in registers", V, FLT_MAX_V);
+    KVQ_REQUIRE(ld % 8 == 0 && ((uintptr_t)logits & 15) == 0, "kvq_gen_select_filtered: ld %% 8 == 0 and 16-byte aligned logits required");
+    KVQ_REQUIRE(((uintptr_t)state & 7) == 0 && ((uintptr_t)filter & 3) == 0 && ((uintptr_t)ids & 7) == 0
+                    && (((uintptr_t)finished | (uintptr_t)lengths | (uintptr_t)step_logits | (uintptr_t)step_kept | (uintptr_t)step_cut
+                         | (uintptr_t)step_logprob) & 3) == 0,
+                "kvq_gen_select_filtered: misaligned state, filter, ids or int32 / f32 buffers");
+    hipStream_t s = (hipStream_t)stream;
+    const GenState* gs = reinterpret_cast<const GenState*>(state);
+    const GenFilter* fs = reinterpret_cast<const GenFilter*>(filter);
+    if (io_dtype == KVQ_F32)
+        hipLaunchKernelGGL(gen_select_filtered_kernel<KVQ_F32>, dim3((unsigned)B), dim3(FLT_THREADS), 0, s, gs, fs, logits, ld, V, ids, finished,
+                           lengths, step_logits, step_kept, step_cut, step_logprob);
+    else
+        hipLaunchKernelGGL(gen_select_filtered_kernel<KVQ_BF16>, dim3((unsigned)B), dim3(FLT_THREADS), 0, s, gs, fs, logits, ld, V, ids, finished,
+                           lengths, step_logits, step_kept, step_cut, step_logprob);
+    return check_launch("gen_select_filtered_kernel");
 }
 
 int kvq_beam_attn(const void* state, const void* q, int64_t ldq, const void* k_new, const void* v_new, int64_t ld_new, void* kv,

@@ -167,6 +167,7 @@ SIGNATURES = {
     "kvq_gen_embed": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _i64, _int, _f32, _int, _vp, _vp]),
     "kvq_gen_attn": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp]),
     "kvq_gen_select": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "kvq_gen_select_filtered": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kvq_gen_gumbel_debug": (_int, [_vp, _i64, _vp, _vp]),
     "kvq_gen_advance": (_int, [_vp, _vp]),
     "kvq_beam_attn": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _int, _int, _vp, _int, _int, _int, _vp, _i64, _vp]),

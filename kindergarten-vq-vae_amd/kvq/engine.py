@@ -463,6 +463,11 @@ class _StepGraphs:
         return res
 
 
+class SamplingRefused(KvqError, TypeError):
+    """A sampling argument (top_k, top_p, temperature, seed, want_scores) handed to beam search: a KvqError naming the argument;
+    a TypeError as well, which is what an unknown keyword is."""
+
+
 class TrainEngine:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False,
                  milestones=None, gamma=0.1, loss_recon_scale=1.0, loss_vq_scale=1.0, seed=1234,
@@ -1927,6 +1932,35 @@ class TrainEngine:
             if lo < 0 or hi >= V:
                 raise KvqError(f"TrainEngine.generate: prompt_ids hold ids outside [0, {V}) (smallest {lo}, largest {hi})")
 
+    @staticmethod
+    def _check_filters(top_k, top_p, temperature, want_scores, V=None):
+        """What generate() refuses about top_k / top_p / want_scores; needs no device.  -> whether the filtered selection runs."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < (1 << 31):
+            raise KvqError(f"TrainEngine.generate: top_k must be an int >= 0 (0 = off), got {top_k!r}")
+        if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not (0.0 < float(top_p) <= 1.0):
+            raise KvqError(f"TrainEngine.generate: top_p must be a finite number in (0, 1] (1 = off), got {top_p!r}")
+        filtered = top_k != 0 or float(top_p) != 1.0
+        if filtered and not float(temperature) > 0.0:
+            raise KvqError(f"TrainEngine.generate: top_k / top_p change nothing at temperature 0 (the arg-max is in every kept set): "
+                           f"got top_k={top_k!r}, top_p={top_p!r} with temperature={temperature!r}")
+        if (filtered or want_scores) and V is not None and V > nnops.GEN_FILTER_MAX_V:
+            raise KvqError(f"TrainEngine.generate: top_k / top_p / want_scores need a vocabulary of at most {nnops.GEN_FILTER_MAX_V} "
+                           f"words (kvq_gen_select_filtered holds a row in registers), this decoder has {V}")
+        return bool(filtered or want_scores)
+
+    _SAMPLING_KEYS = ("top_k", "top_p", "temperature", "seed", "want_scores")
+
+    @classmethod
+    def _refuse_sampling(cls, who, kw):
+        """beam_search takes no sampling argument (sampled beams are out of scope): a KvqError naming them -- one that is also the
+        TypeError such a keyword raised while beam_search had no **kw, so a caller written against either catches it."""
+        given = [k for k in cls._SAMPLING_KEYS if k in kw]
+        if given:
+            raise SamplingRefused(f"TrainEngine.{who}: beam search is deterministic and takes no {', '.join(given)} "
+                           f"(sampling belongs to generate(); sampled beams are not supported)")
+        if kw:
+            raise TypeError(f"TrainEngine.{who}() got an unexpected keyword argument {next(iter(kw))!r}")
+
     def _gen_step(self, g):
         """One position: the decoder layer schedule of _fb_gen on [Bp, H] rows, the token at column t in, the token at t + 1 out.
         Launches only (no host read): the body of the captured graph, and what graph=False runs max_length - 1 times.
@@ -1956,19 +1990,23 @@ class TrainEngine:
         Wv = fl.w("dec.emb.word", rows=self.Vp)
         bv = fl.shadow[fl.seg["head.bias"][0]: fl.seg["head.bias"][0] + self.Vp]
         logits = self._linear(hN, None, None, Wb=(Wv, bv), key="dec.emb.word")                      # [Bp, Vp]
-        if W is None:
+        if W is None and g.get("filter") is not None:       # (top_k, top_p: in the filter state, as temperature and seed in st)
+            nnops.gen_select_filtered(st, g["filter"], logits, self.V, g["ids"], g["finished"], g["lengths"], g["step_logits"], g["kept"],
+                                      g["cut"], g["logprob"])
+        elif W is None:
             nnops.gen_select(st, logits, self.V, g["ids"], g["finished"], g["lengths"], g["step_logits"])  # (temperature, seed: in the state)
         else:
             nnops.beam_select(st, logits, self.V, W, g["ids"], g["parent"], g["scores"], g["step_scores"], g["anc"], g["finished"],
                               g["lengths"], g["step_logits"])
         nnops.gen_advance(st)
 
-    def _gen_buffers(self, B, Se, L, want_logits, graph):
+    def _gen_buffers(self, B, Se, L, want_logits, graph, filtered=False):
         """The buffers of one (B, Se, max_length) -- allocated once, the same addresses in every call -- and, with graph, the captured
         step: position, prompt length, end token, temperature and seed all live in the device state, so one graph serves every call
-        of the shape.  Kept per engine, the oldest of more than _GEN_GRAPHS_KEPT is dropped."""
+        of the shape.  Kept per engine, the oldest of more than _GEN_GRAPHS_KEPT is dropped.  filtered: the variant whose step
+        selects with kvq_gen_select_filtered (top_k and top_p in a filter state of its own), under a key of its own."""
         cache = self._gen_cache
-        key = (B, Se, L, bool(want_logits), self.flat.shadow.data_ptr())
+        key = (B, Se, L, bool(want_logits), self.flat.shadow.data_ptr()) + (("filtered",) if filtered else ())
         g = cache.get(key)
         if g is None:
             dev, H, Bp, nl = self.dev, self.H, _round_up(B, 8), self.n_dec_layers
@@ -1979,6 +2017,9 @@ class TrainEngine:
                      cache=[torch.zeros((Bp, L, 2 * H), dtype=self.dtype, device=dev) for _ in range(nl)],
                      lat=torch.zeros((Bp, Se, H), dtype=self.dtype, device=dev),
                      step_logits=torch.zeros((Bp, L, self.V), dtype=torch.float32, device=dev) if want_logits else None)
+            if filtered:
+                g.update(filter=nnops.new_gen_filter(dev), kept=torch.zeros((Bp, L), dtype=torch.int32, device=dev),
+                         cut=torch.zeros((Bp, L), dtype=torch.int32, device=dev), logprob=torch.zeros((Bp, L), dtype=torch.float32, device=dev))
             if self._cakv_batched:
                 g["kv_all"] = torch.empty((Bp * Se, nl * 2 * H), dtype=self.dtype, device=dev)
                 g["kv"] = [g["kv_all"][:, 2 * H * i: 2 * H * (i + 1)] for i in range(nl)]
@@ -2030,7 +2071,7 @@ class TrainEngine:
         return out
 
     def generate(self, latents, max_length, prompt_ids, eos_id=None, pad_id=None, temperature=0.0, seed=0, quantize=False,
-                 want_logits=False, graph=True):
+                 want_logits=False, graph=True, top_k=0, top_p=1.0, want_scores=False):
         """Free-running generation from a latent: the decoder sees only the prompt and what it has written itself.  latents
         [B, Se, H] as decode() takes them; prompt_ids [B, P] int64 (P >= 1, e.g. a column of start ids) fills columns 0 .. P-1, the
         recurrence  ids[:, t + 1] = choose(logits(latents, ids[:, :t + 1])[t])  the rest up to max_length.  choose: the first arg-max
@@ -2038,12 +2079,21 @@ class TrainEngine:
         finished: lengths = its tokens including the end token, pad_id (default: the embeddings' padding_idx, else 0) behind it.
         One decoder token per sentence and position over a key/value cache (csrc/kvq_generate.hip), no host read inside the loop;
         graph=True replays one captured step max_length - 1 times, graph=False launches it eagerly -- the same bits.
+        top_k >= 1 / top_p < 1 (with temperature > 0) restrict the draw to the top_k most probable tokens and, of those, to the
+        shortest prefix whose renormalised mass reaches top_p (HuggingFace's warpers, k first; ties by the lower id; DESIGN.md
+        section 5k): the selection of the step is kvq_gen_select_filtered, the filters live in a device state beside the
+        generation state, so one captured step serves every (top_k, top_p, temperature, seed).  want_scores: the log-probability
+        of every chosen token under the distribution it was drawn from (at temperature 0: under the full softmax).  With neither,
+        the call is the unfiltered one: the same launches, buffers and captured graph.
         Returns dict(ids [B, max_length], lengths [B], finished [B] bool [, logits [B, max_length - 1, V] f32: row t = what chose
-        column t + 1] [, indices]).  Meaningful for a model trained to predict the NEXT token (DECODER_NEXT_TOKEN); a model trained
+        column t + 1] [, kept [B, max_length - 1] int: the size of the set row t drew from -- with a filter or want_scores]
+        [, token_logprobs [B, max_length - 1] f32, scores [B] f64 = their sum over the positions that CHOSE a token (not the
+        prompt, not the pads behind a finished sentence) -- with want_scores] [, indices]).  Meaningful for a model trained to predict the NEXT token (DECODER_NEXT_TOKEN); a model trained
         on the reference's unshifted loss reproduces its input token by construction."""
         self._latent_call("generate", refresh=False)
         self._check_generate(latents, max_length, prompt_ids, self.H, self.dtype, self.dev, int(self.dcfg.max_position_embeddings), temperature,
                              V=self.V, eos_id=eos_id, pad_id=pad_id, seed=seed)
+        filtered = self._check_filters(top_k, top_p, temperature, want_scores, self.V)
         if quantize and not self.has_vq:
             raise KvqError("TrainEngine.generate: quantize=True, but the model has no quantiser")
         B, Se, _ = latents.shape
@@ -2057,7 +2107,7 @@ class TrainEngine:
                                       quantizer_training=False, stop_after_quantizer=True, want_latents=True, latents=latents)
             latents, res["indices"] = q["z_q"].reshape(B, Se, self.H), q["indices"]
         with torch.no_grad():
-            g = self._gen_buffers(B, Se, L, want_logits, graph)
+            g = self._gen_buffers(B, Se, L, want_logits, graph, filtered)
             Bp = g["Bp"]
             # ---- once per call: the cross-attention keys | values of every layer, the state ----
             g["lat"][:B].copy_(latents)
@@ -2080,6 +2130,11 @@ class TrainEngine:
             g["lengths"].fill_(L)
             if g["step_logits"] is not None:
                 g["step_logits"].zero_()
+            if filtered:
+                g["filter"].copy_(torch.tensor(nnops.gen_filter_words(int(top_k), float(top_p)), dtype=torch.int32), non_blocking=False)
+                g["kept"].zero_()
+                g["cut"].zero_()
+                g["logprob"].zero_()
             # ---- per position ----
             for _ in range(L - 1):
                 if graph:
@@ -2090,6 +2145,13 @@ class TrainEngine:
             res.update(ids=g["ids"][:B].clone(), lengths=g["lengths"][:B].long(), finished=g["finished"][:B] != 0)
             if want_logits:
                 res["logits"] = g["step_logits"][:B, :L - 1].clone()
+            if filtered:
+                res["kept"] = g["kept"][:B, :L - 1].long()
+            if want_scores:                         # row t chose column t + 1: a choice iff P <= t + 1 < lengths
+                lp = g["logprob"][:B, :L - 1].clone()
+                col = torch.arange(1, L, device=self.dev).unsqueeze(0)
+                chose = (col >= P) & (col < res["lengths"].unsqueeze(1))
+                res.update(token_logprobs=lp, scores=torch.where(chose, lp.double(), torch.zeros((), dtype=torch.float64, device=self.dev)).sum(dim=1))
         return res
 
     def generate_codes(self, indices, max_length, prompt_ids, **kw):
@@ -2100,6 +2162,7 @@ class TrainEngine:
         rows = self._code_rows("generate_codes", indices)
         self._check_generate_call(rows.shape[0], max_length, prompt_ids, self.dev, int(self.dcfg.max_position_embeddings),
                                   kw.get("temperature", 0.0), V=self.V, eos_id=kw.get("eos_id"), pad_id=kw.get("pad_id"), seed=kw.get("seed", 0))
+        self._check_filters(kw.get("top_k", 0), kw.get("top_p", 1.0), kw.get("temperature", 0.0), kw.get("want_scores", False), self.V)
         self._seq_limit("generate", rows.shape[1], max_length)
         self._latent_call("generate_codes")         # every refusal above and in here comes before the lookup's launch
         return self.generate(self.codes_to_latents(rows), max_length, prompt_ids, **kw)
@@ -2170,7 +2233,7 @@ class TrainEngine:
             g["step_logits"].zero_()
 
     def beam_search(self, latents, max_length, prompt_ids, num_beams, eos_id=None, pad_id=None, length_penalty=0.0, quantize=False,
-                    want_trace=False, graph=True):
+                    want_trace=False, graph=True, **sampling):
         """The num_beams most probable continuations of the prompt under the free-running decoder of generate(): at every position
         the W = num_beams best of the live hypotheses' W V one-token extensions (by the sum of log-probabilities, ties to the lower
         beam, then the lower token) survive; a hypothesis that chooses eos_id is finished, keeps its score and keeps competing.
@@ -2179,7 +2242,9 @@ class TrainEngine:
         The hypotheses are ranked once, at the end, by score / n^length_penalty (n = generated tokens, at least 1; f64, stable, -inf
         last); pruning inside the search is by the raw sum.  Returns dict(ids [B, L], lengths [B], finished [B]: the best
         hypothesis; beam_ids [B, W, L], beam_scores [B, W] f32 (raw sums), beam_lengths [B, W], beam_finished [B, W]: best first
-        [, trace = dict(ids, parent, step_scores [B, W, L], logits [B, W, L - 1, V] f32), in slot space] [, indices])."""
+        [, trace = dict(ids, parent, step_scores [B, W, L], logits [B, W, L - 1, V] f32), in slot space] [, indices]).
+        top_k, top_p, temperature, seed, want_scores are refused by name: sampled beams are not supported."""
+        self._refuse_sampling("beam_search", sampling)
         self._latent_call("beam_search", refresh=False)
         self._check_beams(num_beams, length_penalty, self.V)
         self._check_generate(latents, max_length, prompt_ids, self.H, self.dtype, self.dev, int(self.dcfg.max_position_embeddings), 0.0,
@@ -2238,6 +2303,7 @@ class TrainEngine:
         """beam_search() of the codebook rows of `indices` [B, Se] / [B, Se, G] int64: as generate_codes is to generate."""
         if kw.get("quantize"):
             raise KvqError("TrainEngine.beam_search_codes: the latents are codebook rows already (quantize=True has nothing to do)")
+        self._refuse_sampling("beam_search_codes", {k: v for k, v in kw.items() if k in self._SAMPLING_KEYS})
         self._latent_call("beam_search_codes", refresh=False)
         rows = self._code_rows("beam_search_codes", indices)
         self._check_beams(num_beams, kw.get("length_penalty", 0.0), self.V)
@@ -2248,15 +2314,26 @@ class TrainEngine:
         return self.beam_search(self.codes_to_latents(rows), max_length, prompt_ids, num_beams, **kw)
 
     def traverse_codes(self, enc_ids, enc_mask, sentence, position, dec_ids=None, dec_mask=None, factor=0, free_running=False,
-                       max_length=None, start_id=None, num_beams=1, length_penalty=0.0):
+                       max_length=None, start_id=None, num_beams=1, length_penalty=0.0, temperature=0.0, seed=0, top_k=0, top_p=1.0,
+                       want_scores=False):
         """Every code at one place of one sentence: encodes the batch, takes sentence `sentence`'s own index rows [Se, G], builds the
         K variants that differ from them only at (position, factor) -- variant k carries code k there -- and decodes them with
         that sentence's decoder ids (default: its encoder ids), at most 256 variants per launch sequence.
         free_running=True: the variants are GENERATED (generate_codes, greedy) from start_id (default: the first decoder id of the
         sentence) up to max_length (default: the decoder ids' length) instead of decoded against the sentence's own ids;
-        num_beams > 1: each variant's row is the best hypothesis of beam_search_codes (length_penalty: its final ranking).
+        num_beams > 1: each variant's row is the best hypothesis of beam_search_codes (length_penalty: its final ranking);
+        temperature, seed, top_k, top_p (num_beams == 1): the variants are SAMPLED as generate() samples; want_scores: scores [K],
+        the sum of the chosen tokens' log-probabilities of every variant (generate's).
         Returns dict(recon_ids [K, Sd], own_code (int), changed [K, Sd] bool: tokens that differ from the own code's row
         [, beam_ids [K, W, Sd], beam_scores [K, W]: every variant's hypotheses, best first, with num_beams = W > 1])."""
+        self._latent_call("traverse_codes", refresh=False)
+        sampling = dict(temperature=temperature, seed=seed, top_k=top_k, top_p=top_p, want_scores=want_scores)
+        if sampling != dict(temperature=0.0, seed=0, top_k=0, top_p=1.0, want_scores=False):
+            if not free_running:
+                raise KvqError("TrainEngine.traverse_codes: temperature, seed, top_k, top_p and want_scores apply with free_running=True")
+            if num_beams != 1:
+                self._refuse_sampling("traverse_codes", {k: v for k, v in sampling.items() if v != dict(temperature=0.0, seed=0, top_k=0, top_p=1.0, want_scores=False)[k]})
+            self._check_filters(top_k, top_p, temperature, want_scores, self.V)
         self._latent_call("traverse_codes")
         if self.vq_kind not in ("VectorQuantizer", "MultiVectorQuantizer"):
             raise KvqError(f"TrainEngine.traverse_codes: needs a VectorQuantizer or MultiVectorQuantizer codebook (this model has "
@@ -2274,7 +2351,7 @@ class TrainEngine:
         K = self.K
         rows = own.unsqueeze(0).repeat(K, 1, 1)
         rows[:, int(position), int(factor)] = torch.arange(K, dtype=torch.int64, device=self.dev)
-        recon, beams = [], []
+        recon, beams, scores = [], [], []
         for k0 in range(0, K, self._TRAVERSE_CHUNK):
             n = min(self._TRAVERSE_CHUNK, K - k0)
             if free_running:
@@ -2282,7 +2359,9 @@ class TrainEngine:
                 gen_args = (rows[k0:k0 + n], int(d_ids.shape[1] if max_length is None else max_length),
                             torch.full((n, 1), start, dtype=torch.int64, device=self.dev))
                 if num_beams == 1:
-                    out = self.generate_codes(*gen_args)
+                    out = self.generate_codes(*gen_args, **sampling)
+                    if want_scores:
+                        scores.append(out["scores"])
                 else:
                     out = self.beam_search_codes(*gen_args, num_beams, length_penalty=length_penalty)
                     beams.append((out["beam_ids"], out["beam_scores"]))
@@ -2295,6 +2374,8 @@ class TrainEngine:
         res = dict(recon_ids=recon, own_code=own_code, changed=recon != recon[own_code].unsqueeze(0))
         if beams:
             res.update(beam_ids=torch.cat([b[0] for b in beams]), beam_scores=torch.cat([b[1] for b in beams]))
+        if scores:
+            res["scores"] = torch.cat(scores)
         return res
 
     def _forward_backward(self, input_ids, attention_mask, training, compute_grads, dec_ids=None, dec_mask=None, want_logits=False,

@@ -629,6 +629,58 @@ def gen_select(state, logits, V, ids, finished, lengths, step_logits=None):
                                lengths.data_ptr(), _p(step_logits), stream_ptr()), "kvq_gen_select")
 
 
+GEN_FILTER_MAX_V = 32768      # the columns kvq_gen_select_filtered holds in registers (csrc/kvq_generate.hip FLT_MAX_V)
+
+
+def gen_filter_words(top_k=0, top_p=1.0):
+    """The four int32 words of a filter state: struct { int32 top_k; float top_p; int32 reserved[2]; } of include/kvq.h.
+    top_k 0 = off, top_p 1 = off."""
+    import struct
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < (1 << 31):
+        raise KvqError(f"a filter state takes top_k as an int >= 0 (0 = off), got {top_k!r}")
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0.0 < float(top_p) <= 1.0:
+        raise KvqError(f"a filter state takes a finite top_p in (0, 1] (1 = off), got {top_p!r}")
+    return [int(top_k), _i32(struct.unpack("<I", struct.pack("<f", float(top_p)))[0]), 0, 0]
+
+
+def new_gen_filter(device, top_k=0, top_p=1.0):
+    """16 bytes beside the generation state: what kvq_gen_select_filtered keeps (gen_filter_words)."""
+    return torch.tensor(gen_filter_words(top_k, top_p), dtype=torch.int32).to(device)
+
+
+def _filter_ptr(filt):
+    if not torch.is_tensor(filt) or filt.dtype != torch.int32 or filt.numel() != 4 or not filt.is_contiguous():
+        raise KvqError("a filter state is new_gen_filter()'s tensor (4 x int32)")
+    require_gpu(filt)
+    return filt.data_ptr()
+
+
+def gen_select_filtered(state, filt, logits, V, ids, finished, lengths, step_logits=None, step_kept=None, step_cut=None, step_logprob=None):
+    """gen_select on the distribution the filter state `filt` (new_gen_filter) leaves: the first top_k of the order (logit
+    descending, then index ascending), of those the shortest prefix whose mass reaches top_p; the same noise, so with the filters
+    off the bits of gen_select.  step_kept / step_cut int32, step_logprob f32, [B, Lmax] each: row (b, t) = the size of the kept
+    set, the id of its last element, the log-probability of the choice under the distribution sampled from (include/kvq.h)."""
+    require_gpu(logits, ids, finished, lengths)
+    B = logits.shape[0]
+    ld = _gen_rows("gen_select_filtered", logits, "logits")
+    if isinstance(V, bool) or not isinstance(V, int) or not 1 <= V <= GEN_FILTER_MAX_V:
+        raise KvqError(f"kvq.nnops.gen_select_filtered: V must be an int in 1 .. {GEN_FILTER_MAX_V} (the columns a workgroup holds), got {V!r}")
+    if ids.dim() != 2 or ids.dtype != torch.int64 or not ids.is_contiguous() or ids.shape[0] != B:
+        raise KvqError("kvq.nnops.gen_select_filtered: ids must be a contiguous int64 [B, Lmax] tensor")
+    for name, x in (("finished", finished), ("lengths", lengths)):
+        if x.dtype != torch.int32 or x.shape != (B,) or not x.is_contiguous():
+            raise KvqError(f"kvq.nnops.gen_select_filtered: {name} must be a contiguous int32 [B] tensor")
+    if step_logits is not None and (step_logits.dtype != torch.float32 or tuple(step_logits.shape) != (B, ids.shape[1], V)
+                                    or not step_logits.is_contiguous()):
+        raise KvqError(f"kvq.nnops.gen_select_filtered: step_logits must be a contiguous float32 [B, Lmax, V] = {(B, ids.shape[1], V)} tensor")
+    for name, x, dt in (("step_kept", step_kept, torch.int32), ("step_cut", step_cut, torch.int32), ("step_logprob", step_logprob, torch.float32)):
+        if x is not None and (x.dtype != dt or tuple(x.shape) != tuple(ids.shape) or not x.is_contiguous()):
+            raise KvqError(f"kvq.nnops.gen_select_filtered: {name} must be a contiguous {dt} [B, Lmax] = {tuple(ids.shape)} tensor")
+    check(lib().kvq_gen_select_filtered(_gen_ptr(state), _filter_ptr(filt), logits.data_ptr(), ld, V, B, io_dtype_of(logits), ids.data_ptr(),
+                                        finished.data_ptr(), lengths.data_ptr(), _p(step_logits), _p(step_kept), _p(step_cut), _p(step_logprob),
+                                        stream_ptr()), "kvq_gen_select_filtered")
+
+
 def gen_gumbel_debug(bits):
     """g [n] f32 = the Gumbel(0, 1) value kvq_gen_select forms from each of the 32-bit patterns bits [n] (int64 holding 0 .. 2^32 - 1,
     or int32 holding the bits): a test hook."""

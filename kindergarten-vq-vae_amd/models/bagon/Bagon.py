@@ -159,10 +159,13 @@ class Bagon(nn.Module):
     def generate_from_latents(self, latents, max_length, prompt_ids, num_beams=1, length_penalty=0.0, **kw):
         """TrainEngine.generate: free-running generation from latents [B, Se, H] -- the decoder sees the prompt [B, P] (e.g. a column
         of start ids) and what it has written itself, one token per position over a key/value cache: dict(ids [B, max_length],
-        lengths, finished [, logits] [, indices]).  kw: eos_id, pad_id, temperature, seed, quantize, want_logits, graph.  Meaningful
+        lengths, finished [, logits] [, kept] [, token_logprobs, scores] [, indices]).  kw: eos_id, pad_id, temperature, seed, top_k,
+        top_p (the draw restricted to the top_k most probable tokens / the shortest prefix of mass top_p),
+        want_scores (the log-probability of every chosen token and their sum), quantize, want_logits, graph.  Meaningful
         for a model trained with DECODER_NEXT_TOKEN.  num_beams > 1: TrainEngine.beam_search instead (section 5j)
         -- the same keys for the best hypothesis, and beam_ids, beam_scores, beam_lengths, beam_finished [B, num_beams, ...] best
-        first; kw: eos_id, pad_id, quantize, want_trace, graph."""
+        first; kw: eos_id, pad_id, quantize, want_trace, graph (top_k, top_p, temperature, seed, want_scores are refused with a KvqError:
+        sampled beams are not supported)."""
         from kvq.engine import engine_of
         if num_beams == 1:
             return engine_of(self).generate(latents, max_length, prompt_ids, **kw)

@@ -92,22 +92,26 @@ class Shelgon(Bagon):
 
     def generate_from_codes(self, indices, max_length, prompt_ids, num_beams=1, length_penalty=0.0, **kw):
         """TrainEngine.generate_codes: the sentence a code sequence produces -- free-running generation (Bagon.generate_from_latents)
-        from the codebook rows of indices [B, Se] / [B, Se, G].  num_beams > 1: TrainEngine.beam_search_codes instead."""
+        from the codebook rows of indices [B, Se] / [B, Se, G]; kw as there (temperature, seed, top_k, top_p, want_scores, ...).
+        num_beams > 1: TrainEngine.beam_search_codes instead, which refuses the sampling keys with a KvqError."""
         from kvq.engine import engine_of
         if num_beams == 1:
             return engine_of(self).generate_codes(indices, max_length, prompt_ids, **kw)
         return engine_of(self).beam_search_codes(indices, max_length, prompt_ids, num_beams, length_penalty=length_penalty, **kw)
 
     def traverse_codes(self, input_ids, attention_mask, sentence, position, decoder_input_ids=None, decoder_attention_mask=None,
-                       factor=0, free_running=False, max_length=None, start_id=None, num_beams=1, length_penalty=0.0):
+                       factor=0, free_running=False, max_length=None, start_id=None, num_beams=1, length_penalty=0.0, temperature=0.0, seed=0,
+                       top_k=0, top_p=1.0, want_scores=False):
         """TrainEngine.traverse_codes: the reconstructions of one sentence under every code at (position, factor):
         dict(recon_ids [K, Sd], own_code, changed [K, Sd]).  free_running=True: the K variants are generated from start_id (default:
-        the sentence's first decoder id) instead of decoded against the sentence's own ids; num_beams > 1: by beam search."""
+        the sentence's first decoder id) instead of decoded against the sentence's own ids; num_beams > 1: by beam search;
+        temperature, seed, top_k, top_p (free running, num_beams == 1): sampled as TrainEngine.generate samples, want_scores: scores [K]."""
         from kvq.engine import engine_of
         return engine_of(self).traverse_codes(input_ids, attention_mask, sentence, position, dec_ids=decoder_input_ids,
                                               dec_mask=decoder_attention_mask, factor=factor, free_running=free_running,
                                               max_length=max_length, start_id=start_id, num_beams=num_beams,
-                                              length_penalty=length_penalty)
+                                              length_penalty=length_penalty, temperature=temperature, seed=seed, top_k=top_k, top_p=top_p,
+                                              want_scores=want_scores)
 
     def forward_loss(self, input_ids, attention_mask, ignore_index=None):
         """Fused step body: (vq_loss, perplexity, indices, loss_recon, acc_per_batch, recon_ids)."""

@@ -21,8 +21,14 @@ what the selection over W V candidates and the reads through the ancestry table 
 tokens of the best hypotheses.  Then the replay of either captured step alone, the census, and the family split of an eager
 beam call.  profiles/beam_search.md records it.
 
+--temperature T (> 0), with --top-k K and / or --top-p P, measures the filtered sampling step instead: the
+unfiltered generate(temperature=T) -- the launches of the parent commit -- against generate(top_k=K), generate(top_p=P), both, and
+want_scores alone, a new seed per call, in alternating rounds; the replay of the unfiltered and of the filtered captured step alone
+(ms per step, the filter state rewritten between the variants: one graph); the census; and kvq_gen_select against
+kvq_gen_select_filtered alone on one [B, V] buffer of N(0, 1) logits.  profiles/sampling_filters.md records it.
+
     PYTHONPATH=kindergarten-vq-vae_amd python3 tools/generate_timing.py [--out FILE.json] [--rounds 5] [--batch 256] [--se 32] [--max-length 32]
-                                                                         [--num-beams W]
+                                                                         [--num-beams W] [--temperature T] [--top-k K] [--top-p P]
 """
 import argparse
 import json
@@ -79,6 +85,78 @@ def beam_timing(a, eng, lat, timed):
     return res
 
 
+def filter_timing(a, eng, lat, prompt, timed):
+    """generate(temperature) unfiltered against top-k, top-p, both and scores alone; then the selection kernels alone"""
+    import torch
+
+    from kvq import nnops
+    B, SE, L, T = a.batch, a.se, a.max_length, a.temperature
+    K, P = a.top_k or 50, a.top_p if a.top_p < 1.0 else 0.9
+    seeds = iter(range(1, 1 << 30))
+    variants = {"top_k": dict(top_k=K), "top_p": dict(top_p=P), "top_k_and_top_p": dict(top_k=K, top_p=P)}
+    arms = {"unfiltered": lambda: eng.generate(lat, L, prompt, temperature=T, seed=next(seeds))["ids"]}
+    for name, kw in variants.items():
+        arms[name] = lambda kw=kw: eng.generate(lat, L, prompt, temperature=T, seed=next(seeds), **kw)["ids"]
+    arms["scores_alone"] = lambda: eng.generate(lat, L, prompt, temperature=T, seed=next(seeds), want_scores=True)["ids"]
+    tokens = B * (L - 1)
+    res = {"model": a.model, "B": B, "Se": SE, "max_length": L, "temperature": T, "top_k": K, "top_p": P, "tokens_per_call": tokens,
+           "rounds": a.rounds, "device": torch.cuda.get_device_name(0)}
+    with torch.no_grad():
+        for fn in arms.values():                                           # warm-up of every arm (the two captures included)
+            fn()
+        times = {k: [] for k in arms}
+        for _ in range(a.rounds):
+            for k, fn in arms.items():
+                times[k].append(timed(fn)[0])
+        for k, v in times.items():
+            ev, ho = sorted(t["event_s"] for t in v), sorted(t["host_s"] for t in v)
+            res[k] = dict(event_s_median=ev[len(ev) // 2], event_s_min=ev[0], event_s_max=ev[-1], host_s_median=ho[len(ho) // 2],
+                          tokens_per_s_median=tokens / ev[len(ev) // 2], ms_per_step_median=1e3 * ev[len(ev) // 2] / (L - 1))
+        res["captured_steps_kept"] = len(eng._gen_cache)                   # two: the unfiltered step and the filtered one
+        passes = max(a.replays // (L - 1), 1)
+        plain = next(g for k, g in eng._gen_cache.items() if "filtered" not in k)
+        filt = next(g for k, g in eng._gen_cache.items() if "filtered" in k)
+
+        def replay_of(entry):
+            def block():                                                   # whole passes over the positions, t back to 0 in front of each
+                for _ in range(passes):
+                    entry["state"][0:1].zero_()
+                    for _ in range(L - 1):
+                        entry["graph"].replay()
+            return block
+        reps = {}
+        for rnd in range(3):                                               # alternated, the median of three
+            eng.generate(lat, L, prompt, temperature=T, seed=5)            # a valid sampling state behind every block
+            reps.setdefault("unfiltered", []).append(timed(replay_of(plain))[0]["event_s"])
+            for name, kw in list(variants.items()) + [("scores_alone", {})]:
+                eng.generate(lat, L, prompt, temperature=T, seed=5, want_scores=True, **kw)
+                reps.setdefault(name, []).append(timed(replay_of(filt))[0]["event_s"])
+        res["graph_replay_ms_per_step"] = {k: 1e3 * sorted(v)[1] / (passes * (L - 1)) for k, v in reps.items()}
+        res["graph_replay_ms_per_step_all"] = {k: [1e3 * x / (passes * (L - 1)) for x in v] for k, v in reps.items()}
+        res["census"] = eng.gen_census()
+        # ---- the selection kernels alone, on one buffer ----
+        V, Vp = eng.V, eng.Vp
+        logits = torch.randn((B, Vp), generator=torch.Generator().manual_seed(2)).to(torch.bfloat16).cuda()
+        ids = torch.zeros((B, 4), dtype=torch.int64, device="cuda")
+        fin, lens = torch.zeros(B, dtype=torch.int32, device="cuda"), torch.full((B,), 4, dtype=torch.int32, device="cuda")
+        kept, cut = torch.zeros((B, 4), dtype=torch.int32, device="cuda"), torch.zeros((B, 4), dtype=torch.int32, device="cuda")
+        lp = torch.zeros((B, 4), dtype=torch.float32, device="cuda")
+        st = nnops.new_gen_state("cuda", 1, 1, 4, None, 0, temperature=T, seed=7)
+        n = 200
+        kern = {}
+
+        def alone(fn):
+            fn()
+            return 1e3 * sorted(timed(lambda: [fn() for _ in range(n)])[0]["event_s"] for _ in range(3))[1] / n
+        kern["kvq_gen_select"] = alone(lambda: nnops.gen_select(st, logits, V, ids, fin, lens))
+        for name, (k, p) in {"off": (0, 1.0), "top_k": (K, 1.0), "top_p": (0, P), "top_k_and_top_p": (K, P)}.items():
+            f = nnops.new_gen_filter("cuda", k, p)
+            kern["kvq_gen_select_filtered_" + name] = alone(lambda f=f: nnops.gen_select_filtered(st, f, logits, V, ids, fin, lens, None, kept, cut, lp))
+        res["selection_kernel_alone_ms"] = kern
+        res["selection_kernel_alone_shape"] = dict(B=B, V=V, ld=Vp, dtype="bfloat16", launches_per_timing=n)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -89,6 +167,9 @@ def main():
     ap.add_argument("--replays", type=int, default=310)
     ap.add_argument("--model", default="bert-base-uncased")
     ap.add_argument("--num-beams", type=int, default=1)
+    ap.add_argument("--temperature", type=float, default=0.0)
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--top-p", type=float, default=1.0)
     a = ap.parse_args()
     import torch
 
@@ -115,8 +196,10 @@ def main():
         torch.cuda.synchronize()
         return dict(host_s=time.perf_counter() - t0, event_s=e0.elapsed_time(e1) * 1e-3), out
 
-    if a.num_beams > 1:
-        res = beam_timing(a, eng, lat, timed)
+    if (a.top_k or a.top_p < 1.0) and not a.temperature > 0:
+        raise SystemExit("--top-k / --top-p measure the sampling step: give --temperature T > 0")
+    if a.num_beams > 1 or a.temperature > 0:
+        res = beam_timing(a, eng, lat, timed) if a.num_beams > 1 else filter_timing(a, eng, lat, prompt, timed)
         text = json.dumps(res, indent=1)
         print(text)
         if a.out:
