@@ -952,6 +952,35 @@ int kvq_beam_gather(const void* state, const int64_t* ids, const int32_t* anc, c
                     void* stream);
 
 
+/* ---- free-running reconstruction metrics (csrc/kvq_seqcmp.hip) ---------------------------------------------
+ * What a generated sentence has to do with the sentence it should have been: token edit distance, positional matches, lengths.
+ * Teacher-forced accuracy (kvq_seq_acc) hands the decoder the true prefix at every position and cannot see a dropped or inserted
+ * word; these kernels compare what kvq_gen_select / kvq_beam_gather wrote with a reference, on the device.  Integers only: the same
+ * inputs give the same bits in any order of execution.  Neither kernel is part of the captured training step.
+ *
+ * kvq_seq_compare  per sentence b:
+ *                    hypothesis h = hyp[b, hyp_skip .. hyp_len[b] - 1], n = hyp_len[b] - hyp_skip tokens (hyp_len: the `lengths` of
+ *                      generation, prompt included; hyp_skip: the prompt length); reference r = ref[b, 0 .. ref_len[b] - 1], m tokens;
+ *                    out[b] = (dist, hits, n, m), int32:
+ *                      dist = the Levenshtein distance of h and r, insertion, deletion and substitution at cost 1 each
+ *                             (n == 0 or m == 0: max(n, m)); the pair is an exact match iff dist == 0;
+ *                      hits = #{j < min(n, m) : h[j] == r[j]}.
+ *                    Tokens are compared on all 64 bits.  0 <= n, m <= Lmax <= 128 (refused above: the launcher knows Lmax only).
+ *                    A row whose lengths on the device lie outside that range -- or past its row: hyp_len[b] > ld_hyp, ref_len[b] >
+ *                    ld_ref -- is not read: out[b] = (-1, 0, 0, 0) and *n_bad += 1 (n_bad: int64 on the device, the caller zeroes
+ *                    it; the pattern of kvq_latent_group_sum).  The other rows are unaffected.
+ *                    One wavefront per pair, four per workgroup; the DP table is walked by anti-diagonals, a lane owning reference
+ *                    columns l + 1 and l + 65 with the last two diagonals in registers and the hypothesis in LDS.  No global
+ *                    scratch; the only atomic is the one on n_bad.  out 16-byte aligned.
+ * kvq_seq_compare_accumulate  for every sentence with dist >= 0 and every column c with 0 <= slot[b, c] < R:
+ *                        table[slot[b, c]] += (1, dist == 0, dist, hits, n, m)            table [R, 6] int64, slot [B, C] int32
+ *                    A slot outside [0, R) is skipped, as is a sentence kvq_seq_compare marked with dist = -1.  64-bit integer
+ *                    atomics: exact, order-free.  One launch, no host read.  R <= 4096, C <= 16; per 16-byte aligned. */
+int kvq_seq_compare(const int64_t* hyp, int64_t ld_hyp, int hyp_skip, const int32_t* hyp_len, const int64_t* ref, int64_t ld_ref,
+                    const int32_t* ref_len, int64_t B, int Lmax, int32_t* out, int64_t* n_bad, void* stream);
+int kvq_seq_compare_accumulate(const int32_t* per, int64_t B, const int32_t* slot, int C, int64_t R, int64_t* table, void* stream);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,10 @@ input_sentence, renumbers them (the old index stays as the column "index", as re
 sentence_acc is the per-sentence accuracy the run's step reported: with LOSS_IGNORE_PAD / KVQ_LOSS_IGNORE_PAD=1 (DESIGN.md section
 5g) that is the accuracy over the sentence's real tokens, so the filter then keeps the sentences whose WORDS were all reconstructed;
 nothing changes here.
+FREE_RUNNING = True (KVQ_FREE_RUNNING) filters on free_running_exact instead: the sentences the latent ALONE gave back when the
+decoder generated from a start token (a run made with FREE_RUNNING_EVAL) -- teacher-forced accuracy hands the
+decoder the true prefix at every position and is not the number that matters for such a model (section 5i).  A table of a run made
+without the option has no such column: an error that names it.
 Constants can be overridden from the environment as KVQ_<NAME>=<python literal>, as in models/shelgon3/config.py.
 """
 import ast
@@ -21,6 +25,7 @@ RUN_ID = "no_checkpoint"
 RUN_DIR = None                       # default: ./runs/<MODEL_NAME>/<RUN_ID>
 DECODED_SENTENCES_DF_PATH = None     # default: <RUN_DIR>/decoded_sentences.feather
 MAX_ACC_THRESHOLD = 0.999
+FREE_RUNNING = False                 # False: sentence_acc > MAX_ACC_THRESHOLD | True: free_running_exact (KVQ_FREE_RUNNING)
 
 for _k in [k for k in list(globals()) if k.isupper()]:
     _v = os.environ.get("KVQ_" + _k)
@@ -59,9 +64,18 @@ def write_table(df, path: str) -> str:
     return base + ".csv"
 
 
-def max_acc_only(decoded_sentences, threshold: float = 0.999):
-    """Rows with sentence_acc > threshold, sorted by input_sentence (ascending), index reset."""
-    kept = decoded_sentences[decoded_sentences["sentence_acc"] > threshold]
+def max_acc_only(decoded_sentences, threshold: float = 0.999, free_running: bool = False):
+    """Rows with sentence_acc > threshold -- free_running: rows whose free_running_exact is true --, sorted by input_sentence
+    (ascending), index reset."""
+    if free_running:
+        if "free_running_exact" not in decoded_sentences.columns:
+            raise KeyError("FREE_RUNNING: the table has no column 'free_running_exact' -- the run was made without FREE_RUNNING_EVAL "
+                           "(models/*/config.py), or none of its decoded stages evaluated free-running")
+        # (a .csv stores the flags as text; rows of stages that did not evaluate are missing values: not kept)
+        flag = decoded_sentences["free_running_exact"].map(lambda v: v is True or str(v).strip().lower() in ("true", "1", "1.0"))
+        kept = decoded_sentences[flag]
+    else:
+        kept = decoded_sentences[decoded_sentences["sentence_acc"] > threshold]
     kept = kept.sort_values(by="input_sentence", ascending=True)
     return kept.reset_index()
 
@@ -69,7 +83,9 @@ def max_acc_only(decoded_sentences, threshold: float = 0.999):
 def main():
     run_dir = RUN_DIR or f"./runs/{MODEL_NAME}/{RUN_ID}"
     src = DECODED_SENTENCES_DF_PATH or f"{run_dir}/decoded_sentences.feather"
-    kept = max_acc_only(read_table(src), MAX_ACC_THRESHOLD)
+    if not isinstance(FREE_RUNNING, bool):
+        raise ValueError(f"FREE_RUNNING (KVQ_FREE_RUNNING) must be True or False, got {FREE_RUNNING!r}")
+    kept = max_acc_only(read_table(src), MAX_ACC_THRESHOLD, FREE_RUNNING)
     out = os.path.splitext(src)[0] + "_max_acc_only"
     try:
         kept.to_markdown(out + ".md", index=False)
@@ -78,7 +94,7 @@ def main():
         with open(out + ".md", "w") as f:
             f.write(kept.to_string(index=False))
     written = write_table(kept, out + ".feather")
-    print(f"{len(kept)} sentences with sentence_acc > {MAX_ACC_THRESHOLD} -> {written}")
+    print(f"{len(kept)} sentences with " + ("free_running_exact" if FREE_RUNNING else f"sentence_acc > {MAX_ACC_THRESHOLD}") + f" -> {written}")
     return kept
 
 

@@ -173,6 +173,8 @@ SIGNATURES = {
     "kvq_beam_attn": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _int, _int, _vp, _int, _int, _int, _vp, _i64, _vp]),
     "kvq_beam_select": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kvq_beam_gather": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
+    "kvq_seq_compare": (_int, [_vp, _i64, _int, _vp, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp]),
+    "kvq_seq_compare_accumulate": (_int, [_vp, _i64, _vp, _int, _i64, _vp, _vp]),
 }
 
 _lib = None

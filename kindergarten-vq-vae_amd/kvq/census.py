@@ -1,6 +1,7 @@
 """Device-resident census tables: the word x code census of the quantiser's indices (host side of `kvq_code_census`,
-include/kvq.h), the attention-map census (`AttentionCensus`, host side of `kvq_attn_probs`) and, at the end of the file, the
-group means of encoder outputs (`LatentCensus`, host side of `kvq_latent_group_sum` / `kvq_latent_shift`).
+include/kvq.h), the attention-map census (`AttentionCensus`, host side of `kvq_attn_probs`), the group means of encoder outputs
+(`LatentCensus`, host side of `kvq_latent_group_sum` / `kvq_latent_shift`) and, at the end of the file, the free-running
+reconstruction metrics summed per generative-factor value (`ReconstructionCensus`, host side of `kvq_seq_compare_accumulate`).
 
 Boundary mirrored: the bookkeeping of analyses/unsupervised_vq_disentanglement/unsupervised_vq_disentanglement.py:156-235.
 The reference walks sentence -> word -> token in Python, tokenising every word of every sentence again to learn how many
@@ -254,3 +255,64 @@ class LatentCensus:
                 raise KvqError(f"LatentCensus.shift: sel must be [B, S] = {tuple(latents.shape[:2])}, got {tuple(sel.shape)}")
             sel = (sel != 0).to(torch.int8).contiguous()
         return nnops.latent_shift(latents, self.table, self.count, int(g1), int(g0), float(alpha), sel=sel, out=out)
+
+
+class ReconstructionCensus:
+    """Free-running reconstruction metrics summed over everything seen: one int64 table [R, 6] of
+    (sentences, exact matches, edit distance, positional hits, hypothesis tokens, reference tokens) and the count of sentences
+    whose lengths did not fit, on the device.  Row 0 is "all sentences"; behind it one row per (factor, value) of the dataset's
+    generative factors, laid out by the prefix sums of `cardinalities` (rows()).  TrainEngine.reconstruct(..., slots=
+    census.slots_of(labels), census=census) adds a batch (kvq_seq_compare_accumulate: integer sums, no host read);
+    result() reads the table back once.  The table may live on the CPU for slots_of / result (tests, merging saved tables);
+    reconstruct needs it on the engine's device."""
+    COLUMNS = ("sentences", "exact", "dist", "hits", "hyp_tokens", "ref_tokens")
+
+    def __init__(self, cardinalities=None, device=None):
+        cards = [] if cardinalities is None else list(cardinalities)
+        if any(isinstance(c, bool) or not isinstance(c, int) or c < 1 for c in cards):
+            raise KvqError(f"ReconstructionCensus: cardinalities must be ints >= 1, got {cardinalities!r}")
+        self.cardinalities = cards
+        self.offsets = [1 + sum(cards[:f]) for f in range(len(cards))]        # first row of factor f
+        self.R = 1 + sum(cards)
+        if self.R > 4096 or len(cards) + 1 > 16:
+            raise KvqError(f"ReconstructionCensus: {self.R} rows / {len(cards)} factors above the kernel's limits (4096 rows, 15 factors)")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.table = torch.zeros((self.R, 6), dtype=torch.int64, device=self.device)
+        self.n_bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def reset(self) -> None:
+        self.table.zero_()
+        self.n_bad.zero_()
+
+    def rows(self):
+        """[(factor, value)] per table row; row 0 is (None, None)."""
+        return [(None, None)] + [(f, v) for f, c in enumerate(self.cardinalities) for v in range(c)]
+
+    def slots_of(self, labels: torch.Tensor) -> torch.Tensor:
+        """labels [B, F] integers (F = number of factors) -> int32 [B, F + 1] on the census' device: column 0 is row 0 for every
+        sentence, column f + 1 the row of (f, labels[b, f]); a label outside its factor's range maps to -1 (skipped).  No host
+        read."""
+        F = len(self.cardinalities)
+        if not torch.is_tensor(labels) or labels.dim() != 2 or labels.shape[1] != F or labels.is_floating_point() or labels.dtype == torch.bool:
+            raise KvqError(f"ReconstructionCensus.slots_of: labels must be an integer [B, {F}] tensor")
+        lab = labels.to(device=self.device, dtype=torch.int64)
+        out = torch.zeros((lab.shape[0], F + 1), dtype=torch.int32, device=self.device)
+        if F:
+            card = torch.tensor(self.cardinalities, dtype=torch.int64, device=self.device)
+            off = torch.tensor(self.offsets, dtype=torch.int64, device=self.device)
+            ok = (lab >= 0) & (lab < card)
+            out[:, 1:] = torch.where(ok, lab + off, torch.full_like(lab, -1)).to(torch.int32)
+        return out
+
+    def result(self) -> dict:
+        """One read-back.  dict(sentences int64 [R], exact, token_acc, edit_rate, len_ratio float64 [R], n_bad int, rows):
+        exact = exact matches / sentences, token_acc = hits / reference tokens, edit_rate = distance / reference tokens,
+        len_ratio = hypothesis tokens / reference tokens; nan for a row without sentences."""
+        flat = torch.cat([self.table.reshape(-1), self.n_bad.reshape(-1)]).cpu()
+        t = flat[:-1].view(self.R, 6)
+        n, ref = t[:, 0], t[:, 5].to(torch.float64)
+        nan = torch.full((self.R,), float("nan"), dtype=torch.float64)
+        some = n > 0
+        per_ref = lambda c: torch.where(some, t[:, c].to(torch.float64) / ref, nan)
+        return dict(sentences=n.clone(), exact=torch.where(some, t[:, 1].to(torch.float64) / n.to(torch.float64), nan),
+                    token_acc=per_ref(3), edit_rate=per_ref(2), len_ratio=per_ref(4), n_bad=int(flat[-1]), rows=self.rows())

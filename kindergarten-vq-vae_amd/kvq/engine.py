@@ -2313,6 +2313,99 @@ class TrainEngine:
         self._latent_call("beam_search_codes")      # every refusal above and in here comes before the lookup's launch
         return self.beam_search(self.codes_to_latents(rows), max_length, prompt_ids, num_beams, **kw)
 
+    # ------------------------------------------------------------------------------------------------------------
+    # free-running reconstruction metrics: encode -> generate from a start token -> compare with the input
+    # ------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_reconstruct(enc_ids, enc_mask, start_id, eos_id, target_ids, target_mask, max_length, slots, census, dev, V, sampling):
+        """What reconstruct() refuses itself (generate / beam_search refuse the rest); needs no device.  -> (targets, their mask or
+        None, max_length)."""
+        given = [k for k in TrainEngine._SAMPLING_KEYS if k in sampling]
+        if given:
+            raise SamplingRefused(f"TrainEngine.reconstruct: an evaluation is deterministic and takes no {', '.join(given)} "
+                                  f"(greedy generation, or beam search with num_beams > 1)")
+        if sampling:
+            raise TypeError(f"TrainEngine.reconstruct() got an unexpected keyword argument {next(iter(sampling))!r}")
+        if not torch.is_tensor(enc_ids) or enc_ids.dim() != 2 or enc_ids.dtype != torch.int64 or enc_ids.shape[0] < 1 or enc_ids.shape[1] < 1:
+            raise KvqError("TrainEngine.reconstruct: enc_ids must be a non-empty int64 [B, S] tensor")
+        if not torch.is_tensor(enc_mask) or enc_mask.shape != enc_ids.shape:
+            raise KvqError("TrainEngine.reconstruct: enc_ids [B, S] needs an enc_mask of its shape")
+        B, S = enc_ids.shape
+        if isinstance(start_id, bool) or not isinstance(start_id, int) or not 0 <= start_id < V:
+            raise KvqError(f"TrainEngine.reconstruct: start_id must be a token id (an int in [0, {V})), got {start_id!r}")
+        if eos_id is not None and (isinstance(eos_id, bool) or not isinstance(eos_id, int) or not 0 <= eos_id < V):
+            raise KvqError(f"TrainEngine.reconstruct: eos_id must be None or a token id (an int in [0, {V})), got {eos_id!r}")
+        if max_length is None:
+            max_length = S + 1
+        if target_ids is None:
+            if target_mask is not None:
+                raise KvqError("TrainEngine.reconstruct: target_mask without target_ids (the encoder's mask goes with its ids)")
+            target_ids, target_mask = enc_ids, enc_mask
+        else:
+            if not torch.is_tensor(target_ids) or target_ids.dim() != 2 or target_ids.dtype != torch.int64 or target_ids.shape[0] != B \
+                    or target_ids.shape[1] < 1 or target_ids.device != dev:
+                raise KvqError(f"TrainEngine.reconstruct: target_ids must be int64 [B, St] with B = {B} on {dev}")
+            if eos_id is not None and target_mask is None:
+                raise KvqError("TrainEngine.reconstruct: with an eos_id, target_ids needs a target_mask (its row sums are the "
+                               "reference lengths)")
+        if target_mask is not None and (not torch.is_tensor(target_mask) or target_mask.shape != target_ids.shape or target_mask.device != dev):
+            raise KvqError(f"TrainEngine.reconstruct: target_mask must have target_ids' shape {tuple(target_ids.shape)} on {dev}")
+        if slots is not None and census is None:
+            raise KvqError("TrainEngine.reconstruct: slots without a census to add them to")
+        if census is not None:
+            from .census import ReconstructionCensus
+            if not isinstance(census, ReconstructionCensus) or census.device != dev:
+                raise KvqError(f"TrainEngine.reconstruct: census must be a kvq.census.ReconstructionCensus on {dev}")
+            if slots is not None and (not torch.is_tensor(slots) or slots.dtype != torch.int32 or slots.dim() != 2 or slots.shape[0] != B
+                                      or not 1 <= slots.shape[1] <= nnops.SEQ_TABLE_MAX_COLS or slots.device != dev):
+                raise KvqError(f"TrainEngine.reconstruct: slots must be int32 [B, C] with B = {B}, C <= {nnops.SEQ_TABLE_MAX_COLS} on {dev} "
+                               f"(ReconstructionCensus.slots_of)")
+        return target_ids, target_mask, max_length
+
+    def reconstruct(self, enc_ids, enc_mask, start_id, eos_id=None, target_ids=None, target_mask=None, max_length=None, num_beams=1,
+                    length_penalty=0.0, slots=None, census=None, want_ids=False, graph=True, **sampling):
+        """Does the latent alone give the sentence back?  encode() (the quantiser in evaluation mode; the latents are z_q, else z),
+        generate() greedily from a column of start_id up to max_length (default S + 1) -- or the best hypothesis of beam_search()
+        with num_beams > 1 --, then kvq_seq_compare of what was written behind the start token against target_ids (default:
+        enc_ids) and, with a census (kvq.census.ReconstructionCensus), kvq_seq_compare_accumulate into its table at the rows
+        `slots` [B, C] int32 (default: row 0 for every sentence).
+        Lengths: with an eos_id the reference is the first sum(target_mask[b]) tokens (default mask: enc_mask) and the hypothesis
+        ends with its end token; without one both sides are every column, pads included (max_length - 1 generated tokens against
+        all of target_ids: the reference project's accuracy convention).
+        Returns device tensors dict(dist, hits, hyp_len, ref_len [B] int32, exact [B] bool, n_bad int64 [1]: the sentences whose
+        lengths did not fit, dist = -1 there [, ids [B, max_length], lengths [B] with want_ids]).  No host read beyond
+        generate()'s prompt-range check.  Refuses what encode / generate / beam_search refuse, and every sampling argument."""
+        self._latent_call("reconstruct", refresh=False)
+        tgt, tmask, L = self._check_reconstruct(enc_ids, enc_mask, start_id, eos_id, target_ids, target_mask, max_length, slots, census,
+                                                self.dev, self.V, sampling)
+        if num_beams != 1:
+            self._check_beams(num_beams, length_penalty, self.V)
+        B, S = enc_ids.shape
+        prompt = torch.full((B, 1), int(start_id), dtype=torch.int64, device=self.dev)
+        self._check_generate_call(B, L, prompt, self.dev, int(self.dcfg.max_position_embeddings), 0.0, eos_id=eos_id)
+        self._seq_limit("reconstruct", S, L, tgt.shape[1])
+        enc = self.encode(enc_ids, enc_mask)
+        lat = (enc["z_q"] if self.has_vq else enc["z"]).reshape(B, S, self.H)
+        if num_beams == 1:
+            gen = self.generate(lat, L, prompt, eos_id=eos_id, graph=graph)
+        else:
+            gen = self.beam_search(lat, L, prompt, num_beams, eos_id=eos_id, length_penalty=length_penalty, graph=graph)
+        with torch.no_grad():
+            ids = gen["ids"]
+            St = tgt.shape[1]
+            ref_len = torch.full((B,), St, dtype=torch.int32, device=self.dev) if eos_id is None else tmask.sum(dim=1).to(torch.int32)
+            n_bad = torch.zeros(1, dtype=torch.int64, device=self.dev)
+            per, _ = nnops.seq_compare(ids, gen["lengths"].to(torch.int32), tgt, ref_len, hyp_skip=1, Lmax=max(L - 1, St), n_bad=n_bad)
+            if census is not None:
+                if slots is None:
+                    slots = torch.zeros((B, 1), dtype=torch.int32, device=self.dev)
+                nnops.seq_compare_accumulate(per, slots.contiguous(), census.table)
+                census.n_bad += n_bad
+            res = dict(dist=per[:, 0], hits=per[:, 1], hyp_len=per[:, 2], ref_len=per[:, 3], exact=per[:, 0] == 0, n_bad=n_bad)
+            if want_ids:
+                res.update(ids=ids, lengths=gen["lengths"])
+        return res
+
     def traverse_codes(self, enc_ids, enc_mask, sentence, position, dec_ids=None, dec_mask=None, factor=0, free_running=False,
                        max_length=None, start_id=None, num_beams=1, length_penalty=0.0, temperature=0.0, seed=0, top_k=0, top_p=1.0,
                        want_scores=False):

@@ -1390,3 +1390,61 @@ def beam_gather(state, ids, anc, lengths, out=None):
     check(lib().kvq_beam_gather(_gen_ptr(state), ids.data_ptr(), anc.data_ptr(), lengths.data_ptr(), R, Lmax, out.data_ptr(), stream_ptr()),
           "kvq_beam_gather")
     return out
+
+
+# ---- free-running reconstruction metrics (include/kvq.h "free-running reconstruction metrics"; csrc/kvq_seqcmp.hip) ---------------
+SEQ_COMPARE_MAX = 128         # tokens per side (csrc/kvq_seqcmp.hip SEQ_MAX)
+SEQ_TABLE_MAX_ROWS, SEQ_TABLE_MAX_COLS = 4096, 16
+
+
+def _seq_rows(who, name, x, B=None):
+    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.int64 or x.stride(1) != 1 or (B is not None and x.shape[0] != B):
+        raise KvqError(f"kvq.nnops.{who}: {name} must be an int64 [B, L] tensor with unit column stride"
+                       + (f" and B = {B}" if B is not None else ""))
+    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
+
+
+def seq_compare(hyp, hyp_len, ref, ref_len, hyp_skip=0, Lmax=None, out=None, n_bad=None):
+    """out [B, 4] int32 = (dist, hits, n, m) per sentence: the token edit distance (unit costs) and the positional matches of
+    hyp[b, hyp_skip : hyp_len[b]] (n tokens) against ref[b, : ref_len[b]] (m tokens); hyp, ref int64 [B, L] (row strides are
+    used), hyp_len, ref_len int32 [B].  Lmax (default: what the rows can hold) bounds n and m and is at most 128; a row with a
+    length outside 0 .. Lmax, or past its row, gets (-1, 0, 0, 0) and adds 1 to n_bad (int64 [1] on the device, accumulated).
+    Returns (out, n_bad); nothing is read back."""
+    require_gpu(hyp, hyp_len, ref, ref_len)
+    B = hyp.shape[0] if torch.is_tensor(hyp) and hyp.dim() == 2 else None
+    ldh, ldr = _seq_rows("seq_compare", "hyp", hyp), _seq_rows("seq_compare", "ref", ref, B)
+    for name, x in (("hyp_len", hyp_len), ("ref_len", ref_len)):
+        if not torch.is_tensor(x) or x.dtype != torch.int32 or tuple(x.shape) != (B,) or not x.is_contiguous():
+            raise KvqError(f"kvq.nnops.seq_compare: {name} must be a contiguous int32 [B] = [{B}] tensor")
+    if isinstance(hyp_skip, bool) or not isinstance(hyp_skip, int):
+        raise KvqError(f"kvq.nnops.seq_compare: hyp_skip must be an int, got {hyp_skip!r}")
+    if Lmax is None:
+        Lmax = max(hyp.shape[1] - max(hyp_skip, 0), ref.shape[1], 0)
+    if out is None:
+        out = torch.empty((B, 4), dtype=torch.int32, device=hyp.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (B, 4) or not out.is_contiguous():
+        raise KvqError(f"kvq.nnops.seq_compare: out must be a contiguous int32 [B, 4] = [{B}, 4] tensor")
+    if n_bad is None:
+        n_bad = torch.zeros(1, dtype=torch.int64, device=hyp.device)
+    elif n_bad.dtype != torch.int64 or n_bad.numel() != 1:
+        raise KvqError("kvq.nnops.seq_compare: n_bad must be one int64 on the device")
+    require_gpu(out, n_bad)
+    check(lib().kvq_seq_compare(hyp.data_ptr(), ldh, hyp_skip, hyp_len.data_ptr(), ref.data_ptr(), ldr, ref_len.data_ptr(), B, int(Lmax),
+                                out.data_ptr(), n_bad.data_ptr(), stream_ptr()), "kvq_seq_compare")
+    return out, n_bad
+
+
+def seq_compare_accumulate(per, slot, table):
+    """table [R, 6] int64 += (1, dist == 0, dist, hits, n, m) of every sentence of per [B, 4] (seq_compare's out) with dist >= 0, at
+    each row slot[b, c] (int32 [B, C]) inside [0, R); other slots are skipped.  Integer sums: the same bits in any order."""
+    require_gpu(per, slot, table)
+    if per.dim() != 2 or per.shape[1] != 4 or per.dtype != torch.int32 or not per.is_contiguous():
+        raise KvqError("kvq.nnops.seq_compare_accumulate: per must be a contiguous int32 [B, 4] tensor")
+    B = per.shape[0]
+    if slot.dim() != 2 or slot.shape[0] != B or slot.dtype != torch.int32 or not slot.is_contiguous():
+        raise KvqError(f"kvq.nnops.seq_compare_accumulate: slot must be a contiguous int32 [B, C] tensor with B = {B}")
+    if table.dim() != 2 or table.shape[1] != 6 or table.dtype != torch.int64 or not table.is_contiguous():
+        raise KvqError("kvq.nnops.seq_compare_accumulate: table must be a contiguous int64 [R, 6] tensor")
+    check(lib().kvq_seq_compare_accumulate(per.data_ptr(), B, slot.data_ptr(), slot.shape[1], table.shape[0], table.data_ptr(),
+                                           stream_ptr()), "kvq_seq_compare_accumulate")
+    return table

@@ -31,6 +31,7 @@ from common.consts import *  # noqa: F401,F403
 from common.tensor_utils import replace_pct_rand_values
 from kvq.runlog import (drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note, optimizer_steps_epoch,
                         weight_ema_epoch_record, weight_ema_scope, lr_epoch_record, param_groups_line)
+from kvq.free_running import FR_KEYS, decoded_columns
 from kvq.train_state import check_every, restore_trainer, save_train_state, trainer_state
 
 
@@ -175,7 +176,9 @@ def end_of_epoch_print(stats_stage_run, stats_stage_best, console, epoch, print_
         f"loss_recon: [bold {stat_color}] {stats_stage_run['loss_recon_run']:08.6f}[/bold {stat_color}] "
         f"{stat_emojis[1] if stats_stage_best['loss_recon_is_best'] else '  '} | "
         f"acc: [bold {stat_color}]{stats_stage_run['metric_acc_run']:08.6f}%[/bold {stat_color}] "
-        f"{stat_emojis[2] if stats_stage_best['metric_acc_is_best'] else '  '} | " + ("\n" if print_new_line else ""))
+        f"{stat_emojis[2] if stats_stage_best['metric_acc_is_best'] else '  '} | " +
+        "".join(f"{k}: [bold {stat_color}]{stats_stage_run[k]:08.6f}[/bold {stat_color}] | " for k in FR_KEYS if k in stats_stage_run) +      # FREE_RUNNING_EVAL
+        ("\n" if print_new_line else ""))
 
 
 def init_stats_best():
@@ -188,8 +191,10 @@ def init_stats_run():
 
 
 def create_wandb_log_dict(epoch: int, stats_stage_run: dict, stage: str):
-    return {"epoch": epoch, f"{stage}/loss_recon": stats_stage_run["loss_recon_run"], f"{stage}/loss_full": stats_stage_run["loss_full_run"],
-            f"{stage}/acc": stats_stage_run["metric_acc_run"], f"padding_tokens_pct/{stage}": stats_stage_run["padding_tokens_pct_run"]}
+    rec = {"epoch": epoch, f"{stage}/loss_recon": stats_stage_run["loss_recon_run"], f"{stage}/loss_full": stats_stage_run["loss_full_run"],
+           f"{stage}/acc": stats_stage_run["metric_acc_run"], f"padding_tokens_pct/{stage}": stats_stage_run["padding_tokens_pct_run"]}
+    rec.update({f"{stage}/{k}": stats_stage_run[k] for k in FR_KEYS if k in stats_stage_run})      # FREE_RUNNING_EVAL: the stage's free-running numbers
+    return rec
 
 
 # the five generative factors the reference spells out per decoded sentence (Trainer.py:205-253): (row key, {label: name})
@@ -207,7 +212,9 @@ def explicit_latent_classes_labels(latent_classes_labels: Tensor, console=None):
 
 
 def decode_sentences(input_ids_encoder, input_ids_decoder, recon_ids, latent_classes_labels, stats_step, tokenizer_encoder,
-                     tokenizer_decoder, decoded_sentences: list, epoch: int, stage: str, console=None):
+                     tokenizer_decoder, decoded_sentences: list, epoch: int, stage: str, console=None, free_running_rec=None):
+    """free_running_rec: a TrainEngine.reconstruct(want_ids=True) result of the batch (FREE_RUNNING_EVAL) -- the rows then also carry
+    free_running_sentence, free_running_edit_distance, free_running_exact."""
     def _decode(tok, ids):
         try:
             return tok.batch_decode(sequences=ids.cpu(), skip_special_tokens=True)
@@ -216,10 +223,13 @@ def decode_sentences(input_ids_encoder, input_ids_decoder, recon_ids, latent_cla
     input_decoded, recon_decoded = _decode(tokenizer_encoder, input_ids_encoder), _decode(tokenizer_decoder, recon_ids)
     accs = stats_step["metric_acc_step_per_sentence"].cpu().tolist()
     labels = latent_classes_labels.cpu() if latent_classes_labels is not None else [None] * len(accs)
-    for i, r, a, l in zip(input_decoded, recon_decoded, accs, labels):
+    extra = decoded_columns(free_running_rec, tokenizer_decoder) if free_running_rec is not None else [None] * len(accs)
+    for i, r, a, l, fr in zip(input_decoded, recon_decoded, accs, labels, extra):
         row = {"epoch": epoch, "stage": stage, "input_sentence": i, "recon_sentence": r, "sentence_acc": a}
         if l is not None:
             row.update(explicit_latent_classes_labels(l, console))
+        if fr is not None:
+            row.update(fr)
         decoded_sentences.append(row)
 
 
@@ -248,8 +258,14 @@ def _batch_size(batch) -> int:
     return len(batch)
 
 
-def _stage(stage, loader, n_batches, step_kw, opt, lr_sched, pcts, decode_into, epoch, grad_sync, engine, prg=None, task=None):
+def _stage(stage, loader, n_batches, step_kw, opt, lr_sched, pcts, decode_into, epoch, grad_sync, engine, prg=None, task=None,
+           free_running=None):
+    """free_running: a kvq.free_running.FreeRunningEval (FREE_RUNNING_EVAL) -- the stages it runs in also generate every batch from
+    its latent and compare it with the decoder's ids on the device; the stage's record gains fr_exact, fr_token_acc, fr_edit_rate."""
     run, n_els, n_steps = init_stats_run(), 0, 0
+    fr_on = free_running is not None and free_running.runs(stage)
+    if fr_on:
+        free_running.begin()
     for batch in islice(loader, n_batches):
         n = _batch_size(batch)
         n_els += n
@@ -257,12 +273,24 @@ def _stage(stage, loader, n_batches, step_kw, opt, lr_sched, pcts, decode_into, 
         with (torch.enable_grad() if opt is not None else no_grad()):
             st, ids_enc, ids_dec, recon, labels = step(opt=opt, lr_sched=lr_sched, batch=batch, encoder_perturb_pct=pcts[0],
                                                        decoder_perturb_pct=pcts[1], grad_sync=grad_sync, engine=engine, **step_kw)
+        fr_rec = None
+        if fr_on:       # the ids are the step's (perturbed as scored); the masks are the batch's
+            dev = step_kw["device"]
+            m_enc = _tokenize(batch, step_kw["tokenizer_encoder"], step_kw["tokenizer_encoder_add_special_tokens"],
+                              step_kw["tokenized_encoder_sentence_max_length"], dev, "encoder")[1]
+            m_dec = m_enc if ids_dec is ids_enc else _tokenize(batch, step_kw["tokenizer_decoder"], step_kw["tokenizer_decoder_add_special_tokens"],
+                                                               step_kw["tokenized_decoder_sentence_max_length"], dev, "decoder")[1]
+            with no_grad():
+                fr_rec = free_running.batch(ids_enc, m_enc, None if ids_dec is ids_enc else ids_dec, None if ids_dec is ids_enc else m_dec,
+                                            labels=labels, want_ids=decode_into is not None)
         if decode_into is not None:
             decode_sentences(ids_enc, ids_dec, recon, labels, st, step_kw["tokenizer_encoder"], step_kw["tokenizer_decoder"],
-                             decode_into, epoch, stage, step_kw.get("console"))
+                             decode_into, epoch, stage, step_kw.get("console"), free_running_rec=fr_rec)
         run = end_of_step_stats_update(run, st, n)
         if prg is not None and task is not None:
             prg.advance(task, 1)
+    if fr_on:
+        run.update(free_running.finish())          # one read of the census, at the end of the stage
     return run, n_els, n_steps
 
 
@@ -272,8 +300,11 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
           encoder_perturb_train_pct, encoder_perturb_val_pct, decoder_perturb_train_pct, decoder_perturb_val_pct,
           n_epochs_to_decode_after, decoded_sentences, opt, lr_sched, n_epochs, vocab_size_encoder, vocab_size_decoder,
           wandb_run, run_path, export_checkpoint=True, grad_sync=None, engine=None, is_main=True,
-          train_state_path=None, train_state_every: int = 1, resume=None, train_state_config=None, weight_ema_eval: bool = True):
-    """weight_ema_eval: with an engine that keeps an average of the weights (TrainEngine(weight_ema=...)), run every validation
+          train_state_path=None, train_state_every: int = 1, resume=None, train_state_config=None, weight_ema_eval: bool = True,
+          free_running=None):
+    """free_running: a kvq.free_running.FreeRunningEval whose validation switch is on makes every validation stage report the
+    free-running numbers too (the best-checkpoint decision does not read them).
+    weight_ema_eval: with an engine that keeps an average of the weights (TrainEngine(weight_ema=...)), run every validation
     stage under it and write the best-val checkpoints while it is applied: they hold the weights that were scored.
     train_state_path: the run's training-state file (kvq.train_state; None: none is written), rewritten at the end of every
     train_state_every-th epoch and of the last one, behind validation and the best checkpoints.  resume: such a file's dict
@@ -336,7 +367,7 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train, n_batches_val
         model.eval()
         with weight_ema_scope(engine, weight_ema_eval):       # weight_ema: validation and the best-val checkpoints under the average
             run, n, s = _stage("val", dl_val, n_batches_val, step_kw, None, None, (encoder_perturb_val_pct, decoder_perturb_val_pct),
-                               dec, epoch, None, engine, prg, tasks and tasks[1])
+                               dec, epoch, None, engine, prg, tasks and tasks[1], free_running=free_running)
             stats_val_run, stats_val_best = end_of_epoch_stats_update(run, stats_val_best, n, s)
             end_of_epoch_print(stats_val_run, stats_val_best, console, epoch, False, COLOR_VAL, STATS_EMOJI_VAL, epoch != n_epochs)
             wandb_run.log(create_wandb_log_dict(epoch, stats_val_run, "val"))
@@ -358,8 +389,9 @@ def test(prg, console, device, dl_test, n_batches_test, model, tokenizer_encoder
          tokenizer_encoder_add_special_tokens, tokenized_encoder_sentence_max_length,
          tokenizer_decoder_add_special_tokens, tokenized_decoder_sentence_max_length,
          encoder_perturb_test_pct, decoder_perturb_test_pct, decoded_sentences, vocab_size_encoder, vocab_size_decoder, epoch,
-         wandb_run, engine=None, weight_ema_eval: bool = True):
-    """weight_ema_eval: with an engine that keeps an average of the weights, score the test split under it (False: under the
+         wandb_run, engine=None, weight_ema_eval: bool = True, free_running=None):
+    """free_running: a kvq.free_running.FreeRunningEval -- the stage also measures free-running reconstruction (FREE_RUNNING_EVAL).
+    weight_ema_eval: with an engine that keeps an average of the weights, score the test split under it (False: under the
     weights the model holds -- what a caller passes who has just loaded a checkpoint that already holds the average)."""
     step_kw = dict(device=device, model=model, tokenizer_encoder=tokenizer_encoder, tokenizer_decoder=tokenizer_decoder,
                    tokenizer_encoder_add_special_tokens=tokenizer_encoder_add_special_tokens,
@@ -370,7 +402,7 @@ def test(prg, console, device, dl_test, n_batches_test, model, tokenizer_encoder
     model.eval()
     with weight_ema_scope(engine, weight_ema_eval):
         run, n, s = _stage("test", dl_test, n_batches_test, step_kw, None, None, (encoder_perturb_test_pct, decoder_perturb_test_pct),
-                           decoded_sentences, epoch, None, engine)
+                           decoded_sentences, epoch, None, engine, free_running=free_running)
     stats_test_run, stats_test_best = end_of_epoch_stats_update(run, init_stats_best(), n, s)
     end_of_epoch_print(stats_test_run, stats_test_best, console, epoch, False, COLOR_TEST, STATS_EMOJI_TEST, True)
     wandb_run.log(create_wandb_log_dict(epoch, stats_test_run, "test"))

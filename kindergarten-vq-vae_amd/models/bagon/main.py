@@ -31,6 +31,7 @@ from dsentences.token_cache import cache_of_split  # noqa: E402
 from kvq import ddp  # noqa: E402
 from kvq._ffi import KvqError  # noqa: E402
 from kvq.engine import TrainEngine  # noqa: E402
+from kvq.free_running import FreeRunningEval, check_free_running_config, label_cardinalities  # noqa: E402
 from kvq.runlog import init_run  # noqa: E402
 from kvq.tokenizer import load_tokenizer  # noqa: E402
 from kvq.train_state import config_differences, load_optimizer, load_train_state, resolve_path  # noqa: E402
@@ -39,6 +40,9 @@ from models.bagon.Trainer import test, train  # noqa: E402
 
 
 def main():
+    # FREE_RUNNING_EVAL: refused here, before anything is set up, when the configuration cannot run it
+    check_free_running_config(FREE_RUNNING_EVAL, FREE_RUNNING_EVAL_VAL, FREE_RUNNING_EVAL_BEAMS, DECODER_NEXT_TOKEN, USE_ENGINE,
+                              int(os.environ.get("WORLD_SIZE", "1") or 1))
     rank, local_rank, world = ddp.init_distributed()
     is_main = rank == 0
     if not torch.cuda.is_available():
@@ -114,6 +118,16 @@ def main():
         from kvq.tokenizer import CLS
         start_id = getattr(tok_dec, "cls_token_id", None)
         model.decoder_next_token_start_id = int(CLS if start_id is None else start_id)
+    free_running = None
+    if FREE_RUNNING_EVAL:       # free-running reconstruction metrics in the test stage (and validation): DESIGN.md section 5l
+        if engine is None:
+            raise ValueError("FREE_RUNNING_EVAL needs the engine (USE_ENGINE and a model shape it supports)")
+        from kvq.tokenizer import SEP
+        eos_id = getattr(tok_dec, "sep_token_id", None)
+        free_running = FreeRunningEval(engine, model.decoder_next_token_start_id,
+                                       eos_id=int(SEP if eos_id is None else eos_id) if TOKENIZER_ADD_SPECIAL_TOKENS else None,
+                                       num_beams=FREE_RUNNING_EVAL_BEAMS, validation=FREE_RUNNING_EVAL_VAL,
+                                       cardinalities=label_cardinalities(ds.latent_classes_labels))
     if engine is None and LOSS_IGNORE_PAD:      # the autograd path: forward_loss hands the pad id to fused_cross_entropy(ignore_index=...)
         model.loss_ignore_index = model.decoder.bert.embeddings.word_embeddings.padding_idx
         if model.loss_ignore_index is None:
@@ -189,7 +203,7 @@ def main():
           run_path=run_path, export_checkpoint=EXPORT_CHECKPOINT, grad_sync=grad_sync, engine=engine, is_main=is_main,
           train_state_path=f"{run_path}/bagon_train_state_last.pth" if EXPORT_TRAIN_STATE else None,
           train_state_every=TRAIN_STATE_EVERY_EPOCHS, resume=resume, train_state_config=state_config,
-          weight_ema_eval=WEIGHT_EMA_EVAL, **common)
+          weight_ema_eval=WEIGHT_EMA_EVAL, free_running=free_running, **common)
     # The test stage runs on EVERY rank (each on its shard of the test split): test() ends in the stage's all-reduce of the
     # statistics (Trainer._sum_over_ranks), a collective every rank has to enter.  Rank 0 wrote the checkpoint; agree() puts a
     # barrier behind that write and hands every rank rank 0's answer to "is there a best checkpoint".
@@ -203,7 +217,10 @@ def main():
              decoded_sentences=decoded, epoch=N_EPOCHS, wandb_run=wandb_run, engine=engine,
              # weight_ema: with WEIGHT_EMA_EVAL the checkpoint just loaded was written under the average and HOLDS the averaged
              # weights that were scored -- they are tested as they are (the scope would put the last epoch's average in their place)
-             weight_ema_eval=False, **common)
+             weight_ema_eval=False, free_running=free_running, **common)
+        if free_running is not None and is_main:
+            from models.bagon.Trainer import _EXPLICIT
+            free_running.write_report(f"{run_path}/reconstruction_by_factor.md", "test", [k for k, _ in _EXPLICIT])
     decoded = ddp.gather_lists(decoded)            # every rank decoded its own shard: rank 0 writes them all
     if is_main:
         import pandas as pd

@@ -26,6 +26,7 @@ from torch import Tensor, no_grad, save
 from common.consts import *  # noqa: F401,F403  (colours / emoji)
 from kvq.runlog import (codes_revived_note, drop_open_accumulation, grad_guard_epoch_record, grad_norm_note, optimizer_step_note,
                         optimizer_steps_epoch, revive_epoch_record, weight_ema_epoch_record, weight_ema_scope, lr_epoch_record, param_groups_line)
+from kvq.free_running import FR_KEYS, decoded_columns
 from kvq.train_state import check_every, restore_trainer, save_train_state, trainer_state
 
 
@@ -174,6 +175,7 @@ def end_of_epoch_print(stats_stage_run, stats_stage_best, console, epoch, print_
     if not isclose(stats_stage_run["metric_perp_run"], -69):
         line += cell("perp", "metric_perp", stat_emojis[3])
     line += cell("acc", "metric_acc", stat_emojis[2], "%")
+    line += "".join(f"{k}: [bold {stat_color}] {stats_stage_run[k]:08.6f}[/bold {stat_color}] | " for k in FR_KEYS if k in stats_stage_run)      # FREE_RUNNING_EVAL
     console.print(line + ("\n" if print_new_line else ""))
 
 
@@ -189,16 +191,24 @@ def init_stats_run():
 
 
 def create_wandb_log_dict(epoch: int, stats_stage_run: dict, stage: str):
-    return {"epoch": epoch,
-            f"{stage}/loss_recon": stats_stage_run["loss_recon_run"], f"{stage}/loss_vq": stats_stage_run["loss_vq_run"],
-            f"{stage}/metric_perp": stats_stage_run["metric_perp_run"], f"{stage}/loss_full": stats_stage_run["loss_full_run"],
-            f"{stage}/acc": stats_stage_run["metric_acc_run"],
-            f"padding_tokens_pct/{stage}": stats_stage_run["padding_tokens_pct_run"]}
+    rec = {"epoch": epoch,
+           f"{stage}/loss_recon": stats_stage_run["loss_recon_run"], f"{stage}/loss_vq": stats_stage_run["loss_vq_run"],
+           f"{stage}/metric_perp": stats_stage_run["metric_perp_run"], f"{stage}/loss_full": stats_stage_run["loss_full_run"],
+           f"{stage}/acc": stats_stage_run["metric_acc_run"],
+           f"padding_tokens_pct/{stage}": stats_stage_run["padding_tokens_pct_run"]}
+    rec.update({f"{stage}/{k}": stats_stage_run[k] for k in FR_KEYS if k in stats_stage_run})      # FREE_RUNNING_EVAL: the stage's free-running numbers
+    return rec
 
 
-def decode_sentences(input_ids, recon_ids, tokenizer, decoded_sentences: list, epoch: int, stage: str, console=None):
-    for i, r in zip(tokenizer.batch_decode(sequences=input_ids.cpu()), tokenizer.batch_decode(sequences=recon_ids.cpu())):
-        decoded_sentences.append({"epoch": epoch, "stage": stage, "input_sentence": i, "recon_sentence": r})
+def decode_sentences(input_ids, recon_ids, tokenizer, decoded_sentences: list, epoch: int, stage: str, console=None, free_running_rec=None):
+    """free_running_rec: a TrainEngine.reconstruct(want_ids=True) result of the batch (FREE_RUNNING_EVAL) -- the rows then also carry
+    free_running_sentence, free_running_edit_distance, free_running_exact."""
+    extra = decoded_columns(free_running_rec, tokenizer) if free_running_rec is not None else [None] * int(input_ids.shape[0])
+    for i, r, fr in zip(tokenizer.batch_decode(sequences=input_ids.cpu()), tokenizer.batch_decode(sequences=recon_ids.cpu()), extra):
+        row = {"epoch": epoch, "stage": stage, "input_sentence": i, "recon_sentence": r}
+        if fr is not None:
+            row.update(fr)
+        decoded_sentences.append(row)
 
 
 def _save_ckpt(model, checkpoint_file_path: str, stage: str):
@@ -227,9 +237,14 @@ def _batch_size(batch) -> int:
 
 
 def _run_stage(stage, device, loader, n_batches, model, tokenizer, tokenizer_add_special_tokens, opt, lr_sched, weights,
-               vocab_size, decode_into, epoch, console, max_length, grad_sync, on_batch=None, engine=None):
+               vocab_size, decode_into, epoch, console, max_length, grad_sync, on_batch=None, engine=None, free_running=None):
+    """free_running: a kvq.free_running.FreeRunningEval (FREE_RUNNING_EVAL) -- the stages it runs in also generate every batch from
+    its latent and compare it with the input on the device; the stage's record gains fr_exact, fr_token_acc, fr_edit_rate."""
     stats_run = init_stats_run()
     n_els_epoch = n_steps = 0
+    fr_on = free_running is not None and free_running.runs(stage)
+    if fr_on:
+        free_running.begin()
     for batch in islice(loader, n_batches):
         n_els_batch = _batch_size(batch)
         n_els_epoch += n_els_batch
@@ -240,11 +255,19 @@ def _run_stage(stage, device, loader, n_batches, model, tokenizer, tokenizer_add
                 device=device, model=model, tokenizer=tokenizer, tokenizer_add_special_tokens=tokenizer_add_special_tokens,
                 opt=opt, lr_sched=lr_sched, batch=batch, vocab_size=vocab_size, stage=stage, console=console,
                 max_length=max_length, grad_sync=grad_sync, engine=engine, **weights)
+        fr_rec = None
+        if fr_on:
+            mask = tokenize_batch(batch, tokenizer, tokenizer_add_special_tokens, max_length, device)[1]
+            with no_grad():
+                fr_rec = free_running.batch(input_ids, mask, labels=batch.get("latent_classes_labels") if isinstance(batch, dict) else None,
+                                            want_ids=decode_into is not None)
         if decode_into is not None:
-            decode_sentences(input_ids, recon_ids, tokenizer, decode_into, epoch, stage, console)
+            decode_sentences(input_ids, recon_ids, tokenizer, decode_into, epoch, stage, console, free_running_rec=fr_rec)
         stats_run = end_of_step_stats_update(stats_run, stats_step, n_els_batch)
         if on_batch:
             on_batch()
+    if fr_on:
+        stats_run.update(free_running.finish())          # one read of the census, at the end of the stage
     return stats_run, n_els_epoch, n_steps
 
 
@@ -254,8 +277,10 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
           loss_perp_rescale_factor: float, loss_perp_weight: float, lr_sched, n_epochs: int, vocab_size: int,
           wandb_run, run_path: str, export_checkpoint: bool, max_length: int = 12, grad_sync=None, is_main: bool = True,
           engine=None, train_state_path=None, train_state_every: int = 1, resume=None, train_state_config=None,
-          weight_ema_eval: bool = True):
-    """weight_ema_eval: with an engine that keeps an average of the weights (TrainEngine(weight_ema=...)), run every validation
+          weight_ema_eval: bool = True, free_running=None):
+    """free_running: a kvq.free_running.FreeRunningEval whose validation switch is on makes every validation stage report the
+    free-running numbers too (the best-checkpoint decision does not read them).
+    weight_ema_eval: with an engine that keeps an average of the weights (TrainEngine(weight_ema=...)), run every validation
     stage under it and write the best-val checkpoints while it is applied: they hold the weights that were scored.
     train_state_path: the run's training-state file (kvq.train_state; None: none is written), rewritten at the end of every
     train_state_every-th epoch and of the last one, behind validation and the best checkpoints.  resume: such a file's dict
@@ -327,7 +352,7 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
         with weight_ema_scope(engine, weight_ema_eval):       # weight_ema: validation and the best-val checkpoints under the average
             run, n_els, n_steps = _run_stage("val", device, dl_val, n_batches_val, model, tokenizer, tokenizer_add_special_tokens,
                                              None, None, weights, vocab_size, decode_now, epoch, console, max_length, None, tick,
-                                             engine=engine)
+                                             engine=engine, free_running=free_running)
             stats_val_run, stats_val_best = end_of_epoch_stats_update(run, stats_val_best, n_els, n_steps)
             end_of_epoch_print(stats_val_run, stats_val_best, console, epoch, False, COLOR_VAL, STATS_EMOJI_VAL, epoch != n_epochs)
             wandb_run.log(create_wandb_log_dict(epoch, stats_val_run, "val"))
@@ -346,8 +371,9 @@ def train(prg, console, device, dl_train, dl_val, n_batches_train: int, n_batche
 def test(prg, console, device, dl_test, n_batches_test, model, tokenizer, tokenizer_add_special_tokens: bool,
          loss_recon_rescale_factor: float, loss_recon_weight: float, loss_vq_rescale_factor: float, loss_vq_weight: float,
          loss_perp_rescale_factor: float, loss_perp_weight: float, decoded_sentences: list, vocab_size: int, epoch: int,
-         wandb_run, max_length: int = 12, engine=None, weight_ema_eval: bool = True):
-    """weight_ema_eval: with an engine that keeps an average of the weights, score the test split under it (False: under the
+         wandb_run, max_length: int = 12, engine=None, weight_ema_eval: bool = True, free_running=None):
+    """free_running: a kvq.free_running.FreeRunningEval -- the stage also measures free-running reconstruction (FREE_RUNNING_EVAL).
+    weight_ema_eval: with an engine that keeps an average of the weights, score the test split under it (False: under the
     weights the model holds -- what a caller passes who has just loaded a checkpoint that already holds the average)."""
     weights = dict(loss_recon_rescale_factor=loss_recon_rescale_factor, loss_recon_weight=loss_recon_weight,
                    loss_vq_rescale_factor=loss_vq_rescale_factor, loss_vq_weight=loss_vq_weight,
@@ -357,7 +383,8 @@ def test(prg, console, device, dl_test, n_batches_test, model, tokenizer, tokeni
     with weight_ema_scope(engine, weight_ema_eval):
         run, n_els, n_steps = _run_stage("test", device, dl_test, n_batches_test, model, tokenizer, tokenizer_add_special_tokens,
                                          None, None, weights, vocab_size, decoded_sentences, epoch, console, max_length, None,
-                                         (lambda: prg.advance(task, 1)) if task is not None else None, engine=engine)
+                                         (lambda: prg.advance(task, 1)) if task is not None else None, engine=engine,
+                                         free_running=free_running)
     stats_test_run, stats_test_best = end_of_epoch_stats_update(run, init_stats_best(), n_els, n_steps)
     end_of_epoch_print(stats_test_run, stats_test_best, console, epoch, False, COLOR_TEST, STATS_EMOJI_TEST, True)
     wandb_run.log(create_wandb_log_dict(epoch, stats_test_run, "test"))

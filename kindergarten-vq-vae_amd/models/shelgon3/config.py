@@ -41,6 +41,9 @@ WEIGHT_EMA_DECAY = None            # None (off) | float in (0, 1): the engine ke
 WEIGHT_EMA_EVAL = True              # with WEIGHT_EMA_DECAY: validation, the best-val checkpoints and the test stage run under the average (False: the average is kept and saved with the training state, evaluation reads the live weights)
 LOSS_IGNORE_PAD = False             # False | True: the engine step takes the reconstruction loss, the accuracy and the per-sentence accuracy over the tokens whose target is not the pad id (F.cross_entropy's ignore_index) instead of over all B*S positions; KVQ_LOSS_IGNORE_PAD; DESIGN.md section 5g
 DECODER_NEXT_TOKEN = False          # False | True: next-token training -- the decoder reads shift_right(ids, [CLS]) and its logits at t are scored against ids[t] (target_ids), instead of the reference's unshifted loss, under which a causal decoder is scored against the token it has just been given and learns to copy it; needs the engine; free-running generation (TrainEngine.generate) is meaningful only for a model trained this way; DESIGN.md section 5i
+FREE_RUNNING_EVAL = False           # False | True: the test stage also measures FREE-RUNNING reconstruction -- encode, generate from the start token on the key/value-cache decoder, compare with the input on the device (exact match, token edit distance, positional matches; TrainEngine.reconstruct): fr_exact / fr_token_acc / fr_edit_rate in the stage line and log, free_running_* columns in decoded_sentences.*, reconstruction_by_factor.md; needs DECODER_NEXT_TOKEN, the engine and a single process; the best-checkpoint decision does not change; KVQ_FREE_RUNNING_EVAL; DESIGN.md section 5l
+FREE_RUNNING_EVAL_VAL = False       # with FREE_RUNNING_EVAL: every validation stage measures it as well (one generation per validation batch and epoch)
+FREE_RUNNING_EVAL_BEAMS = 1         # int in 1 .. 8: 1 = greedy generation, more = the best hypothesis of a beam search of that width
 PARAM_GROUPS = None                 # None (off) | list of {"match": pattern | [patterns], "lr_scale": float >= 0 (1), "weight_decay": float >= 0 (WEIGHT_DECAY)}: fnmatch patterns over the engine's parameter names (engine.param_names()), first match wins, the rest trains under LR and WEIGHT_DECAY; e.g. [{"match": ["*.b", "*.ln.w", "*.ln2.w", "head.bias"], "weight_decay": 0.0}] (= kvq.engine.NO_DECAY); KVQ_PARAM_GROUPS (JSON); DESIGN.md section 5h
 DECOUPLED_WEIGHT_DECAY = False      # False | True: torch.optim.AdamW's decoupled decay instead of Adam's coupled L2 term, in the engine's Adam kernel; KVQ_DECOUPLED_WD (0 / 1)
 LR_WARMUP_STEPS = 0                 # int >= 0: the rate climbs as t / LR_WARMUP_STEPS over the first optimiser steps (0: off); multiplies the MultiStepLR factor
@@ -141,6 +144,13 @@ if DECODER_NEXT_TOKEN in (0, 1) and not isinstance(DECODER_NEXT_TOKEN, bool) and
     DECODER_NEXT_TOKEN = bool(DECODER_NEXT_TOKEN)      # the environment may spell the switch 0 / 1, as KVQ_LOSS_IGNORE_PAD
 if not isinstance(DECODER_NEXT_TOKEN, bool):
     raise ValueError(f"DECODER_NEXT_TOKEN (KVQ_DECODER_NEXT_TOKEN) must be True or False (0 or 1 in the environment), got {DECODER_NEXT_TOKEN!r}")
+for _k in ("FREE_RUNNING_EVAL", "FREE_RUNNING_EVAL_VAL"):      # the environment may spell the switches 0 / 1, as KVQ_DECODER_NEXT_TOKEN
+    if globals()[_k] in (0, 1) and not isinstance(globals()[_k], bool) and _os.environ.get("KVQ_" + _k, "").strip() in ("0", "1"):
+        globals()[_k] = bool(globals()[_k])
+    if not isinstance(globals()[_k], bool):
+        raise ValueError(f"{_k} (KVQ_{_k}) must be True or False (0 or 1 in the environment), got {globals()[_k]!r}")
+if isinstance(FREE_RUNNING_EVAL_BEAMS, bool) or not isinstance(FREE_RUNNING_EVAL_BEAMS, int) or not 1 <= FREE_RUNNING_EVAL_BEAMS <= 8:
+    raise ValueError(f"FREE_RUNNING_EVAL_BEAMS (KVQ_FREE_RUNNING_EVAL_BEAMS) must be an integer in 1 .. 8, got {FREE_RUNNING_EVAL_BEAMS!r}")
 _v = _os.environ.get("KVQ_DECOUPLED_WD", "").strip()      # the variable TrainEngine itself reads; it wins over KVQ_DECOUPLED_WEIGHT_DECAY; empty = unset
 if _v:
     DECOUPLED_WEIGHT_DECAY = {"0": False, "1": True}.get(_v, _v)

@@ -34,6 +34,7 @@ from dsentences.token_cache import cache_of_split  # noqa: E402
 from kvq import ddp  # noqa: E402
 from kvq._ffi import KvqError  # noqa: E402
 from kvq.engine import TrainEngine  # noqa: E402
+from kvq.free_running import FreeRunningEval, check_free_running_config, label_cardinalities  # noqa: E402
 from kvq.runlog import init_run  # noqa: E402
 from kvq.tokenizer import load_tokenizer  # noqa: E402
 from kvq.train_state import config_differences, load_optimizer, load_train_state, resolve_path  # noqa: E402
@@ -45,6 +46,9 @@ from models.shelgon3.VectorQuantizer import VectorQuantizer  # noqa: E402
 
 
 def main():
+    # FREE_RUNNING_EVAL: refused here, before anything is set up, when the configuration cannot run it
+    check_free_running_config(FREE_RUNNING_EVAL, FREE_RUNNING_EVAL_VAL, FREE_RUNNING_EVAL_BEAMS, DECODER_NEXT_TOKEN, USE_ENGINE,
+                              int(os.environ.get("WORLD_SIZE", "1") or 1))
     rank, local_rank, world = ddp.init_distributed()
     is_main = rank == 0
     if not torch.cuda.is_available():
@@ -99,7 +103,7 @@ def main():
     tokenizer = load_tokenizer(TOKENIZER_NAME)
     if TOKEN_CACHE:
         # every split tokenised once and kept in HBM; a batch is an index_select on the device (no per-step tokenizer / H2D)
-        caches = [cache_of_split(sp, tokenizer, TOKENIZED_SENTENCE_MAX_LENGTH, TOKENIZER_ADD_SPECIAL_TOKENS, device)
+        caches = [cache_of_split(sp, tokenizer, TOKENIZED_SENTENCE_MAX_LENGTH, TOKENIZER_ADD_SPECIAL_TOKENS, device, keep_labels=FREE_RUNNING_EVAL)
                   for sp in (ds_train, ds_val, ds_test)]
         dl_train = caches[0].loader(BATCH_SIZE, True, seed=DS_GEN_SEED, rank=rank, world=world)
         dl_val = caches[1].loader(BATCH_SIZE, False, rank=rank, world=world)
@@ -136,6 +140,16 @@ def main():
         from kvq.tokenizer import CLS
         start_id = getattr(tokenizer, "cls_token_id", None)
         model.decoder_next_token_start_id = int(CLS if start_id is None else start_id)
+    free_running = None
+    if FREE_RUNNING_EVAL:       # free-running reconstruction metrics in the test stage (and validation): DESIGN.md section 5l
+        if engine is None:
+            raise ValueError("FREE_RUNNING_EVAL needs the engine (USE_ENGINE and a model shape it supports)")
+        from kvq.tokenizer import SEP
+        eos_id = getattr(tokenizer, "sep_token_id", None)
+        free_running = FreeRunningEval(engine, model.decoder_next_token_start_id,
+                                       eos_id=int(SEP if eos_id is None else eos_id) if TOKENIZER_ADD_SPECIAL_TOKENS else None,
+                                       num_beams=FREE_RUNNING_EVAL_BEAMS, validation=FREE_RUNNING_EVAL_VAL,
+                                       cardinalities=label_cardinalities(ds.latent_classes_labels))
     if engine is None and LOSS_IGNORE_PAD:      # the autograd path: forward_loss hands the pad id to fused_cross_entropy(ignore_index=...)
         model.loss_ignore_index = model.decoder.bert.embeddings.word_embeddings.padding_idx
         if model.loss_ignore_index is None:
@@ -216,7 +230,7 @@ def main():
           max_length=TOKENIZED_SENTENCE_MAX_LENGTH, grad_sync=grad_sync, is_main=is_main, engine=engine,
           train_state_path=f"{run_path}/shelgon_train_state_last.pth" if EXPORT_TRAIN_STATE else None,
           train_state_every=TRAIN_STATE_EVERY_EPOCHS, resume=resume, train_state_config=state_config,
-          weight_ema_eval=WEIGHT_EMA_EVAL, **weights)
+          weight_ema_eval=WEIGHT_EMA_EVAL, free_running=free_running, **weights)
 
     # The test stage runs on EVERY rank (each on its shard of the test split): test() ends in the stage's all-reduce of the
     # statistics (Trainer._sum_over_ranks), a collective every rank has to enter.  Rank 0 wrote the checkpoint; agree() puts a
@@ -232,7 +246,9 @@ def main():
              vocab_size=VOCAB_SIZE, epoch=N_EPOCHS, wandb_run=wandb_run, max_length=TOKENIZED_SENTENCE_MAX_LENGTH, engine=engine,
              # weight_ema: with WEIGHT_EMA_EVAL the checkpoint just loaded was written under the average and HOLDS the averaged
              # weights that were scored -- they are tested as they are (the scope would put the last epoch's average in their place)
-             weight_ema_eval=False, **weights)
+             weight_ema_eval=False, free_running=free_running, **weights)
+        if free_running is not None and is_main:
+            free_running.write_report(f"{run_path}/reconstruction_by_factor.md", "test")
     decoded_sentences = ddp.gather_lists(decoded_sentences)      # every rank decoded its own shard: rank 0 writes them all
     if is_main:
         if prg is not None:

@@ -27,8 +27,14 @@ want_scores alone, a new seed per call, in alternating rounds; the replay of the
 (ms per step, the filter state rewritten between the variants: one graph); the census; and kvq_gen_select against
 kvq_gen_select_filtered alone on one [B, V] buffer of N(0, 1) logits.  profiles/sampling_filters.md records it.
 
+--reconstruct measures TrainEngine.reconstruct instead: encode + generate of B sentences of S = --se tokens,
+max_length S + 1 -- the calls an evaluation would make by hand, and all there is to measure on a commit without reconstruct(), where
+the mode times that arm alone -- against reconstruct() with and without a census of 9 factors, in alternating rounds; then
+kvq_seq_compare and kvq_seq_compare_accumulate alone on the call's own ids.  The shader clock held across the rounds is recorded
+(kvq_clock_probe before and behind them).  profiles/free_running_eval.md records it.
+
     PYTHONPATH=kindergarten-vq-vae_amd python3 tools/generate_timing.py [--out FILE.json] [--rounds 5] [--batch 256] [--se 32] [--max-length 32]
-                                                                         [--num-beams W] [--temperature T] [--top-k K] [--top-p P]
+                                                                         [--num-beams W] [--temperature T] [--top-k K] [--top-p P] [--reconstruct]
 """
 import argparse
 import json
@@ -157,6 +163,66 @@ def filter_timing(a, eng, lat, prompt, timed):
     return res
 
 
+def reconstruct_timing(a, eng, timed):
+    """encode + generate by hand against reconstruct() (without and with a census), then the two comparison kernels alone"""
+    import torch
+
+    from kvq import nnops
+    B, S = a.batch, a.se
+    L = S + 1
+    g = torch.Generator().manual_seed(3)
+    lens = torch.randint(S // 2, S + 1, (B,), generator=g)
+    keep = torch.arange(S)[None] < lens[:, None]
+    ids = (torch.randint(1000, 30000, (B, S), generator=g) * keep).cuda()
+    mask = keep.long().cuda()
+    prompt = torch.full((B, 1), 101, dtype=torch.int64, device="cuda")
+
+    def by_hand():
+        lat = eng.encode(ids, mask)["z"].reshape(B, S, eng.H)
+        return eng.generate(lat, L, prompt)["ids"]
+    arms = {"encode_generate": by_hand}
+    has = hasattr(eng, "reconstruct")
+    if has:
+        from kvq.census import ReconstructionCensus
+        cards = [2, 3, 2, 3, 2, 4, 4, 3, 5]
+        census = ReconstructionCensus(cards)
+        labels = torch.stack([torch.randint(0, c, (B,), generator=g) for c in cards], dim=1).cuda()
+        arms["reconstruct"] = lambda: eng.reconstruct(ids, mask, 101)["dist"]
+        arms["reconstruct_census"] = lambda: eng.reconstruct(ids, mask, 101, slots=census.slots_of(labels), census=census)["dist"]
+    res = {"model": a.model, "B": B, "S": S, "max_length": L, "rounds": a.rounds, "has_reconstruct": has, "device": torch.cuda.get_device_name(0)}
+    with torch.no_grad():
+        for fn in arms.values():                                           # warm-up of every arm (the capture included)
+            fn()
+        times = {k: [] for k in arms}
+        p0 = nnops.clock_probe()
+        for _ in range(a.rounds):                                          # alternating rounds
+            for k, fn in arms.items():
+                times[k].append(timed(fn)[0])
+        p1 = nnops.clock_probe()
+        torch.cuda.synchronize()
+        res["shader_clock_mhz_over_the_rounds"] = nnops.clock_mhz(p0, p1)[0]
+        for k, v in times.items():
+            ev, ho = sorted(t["event_s"] for t in v), sorted(t["host_s"] for t in v)
+            res[k] = dict(event_ms_median=1e3 * ev[len(ev) // 2], event_ms_min=1e3 * ev[0], event_ms_max=1e3 * ev[-1],
+                          host_ms_median=1e3 * ho[len(ho) // 2], host_ms_min=1e3 * ho[0], host_ms_max=1e3 * ho[-1])
+        if has:
+            gen = eng.reconstruct(ids, mask, 101, want_ids=True)
+            hyp, hyp_len = gen["ids"], gen["lengths"].to(torch.int32)
+            ref_len = torch.full((B,), S, dtype=torch.int32, device="cuda")
+            out, bad = nnops.seq_compare(hyp, hyp_len, ids, ref_len, hyp_skip=1, Lmax=S)
+            slots, n = census.slots_of(labels), 200
+
+            def alone(fn):
+                fn()
+                return 1e3 * sorted(timed(lambda: [fn() for _ in range(n)])[0]["event_s"] for _ in range(3))[1] / n
+            res["kernels_alone_us"] = {
+                "kvq_seq_compare": 1e3 * alone(lambda: nnops.seq_compare(hyp, hyp_len, ids, ref_len, hyp_skip=1, Lmax=S, out=out, n_bad=bad)),
+                "kvq_seq_compare_accumulate": 1e3 * alone(lambda: nnops.seq_compare_accumulate(out, slots, census.table))}
+            res["kernels_alone_shape"] = dict(B=B, n=S, m=S, slot_columns=len(cards) + 1, table_rows=census.R, launches_per_timing=n)
+            res["mean_edit_distance_of_the_untrained_model"] = float(gen["dist"].float().mean())
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -170,6 +236,7 @@ def main():
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--reconstruct", action="store_true")
     a = ap.parse_args()
     import torch
 
@@ -198,8 +265,9 @@ def main():
 
     if (a.top_k or a.top_p < 1.0) and not a.temperature > 0:
         raise SystemExit("--top-k / --top-p measure the sampling step: give --temperature T > 0")
-    if a.num_beams > 1 or a.temperature > 0:
-        res = beam_timing(a, eng, lat, timed) if a.num_beams > 1 else filter_timing(a, eng, lat, prompt, timed)
+    if a.num_beams > 1 or a.temperature > 0 or a.reconstruct:
+        res = reconstruct_timing(a, eng, timed) if a.reconstruct else \
+            beam_timing(a, eng, lat, timed) if a.num_beams > 1 else filter_timing(a, eng, lat, prompt, timed)
         text = json.dumps(res, indent=1)
         print(text)
         if a.out:
