@@ -49,7 +49,7 @@ def score_tol(lse, lp, s):
 
 
 def new_state(B, W, L, prompt, pad, R=None):
-    """The start of a search as TrainEngine._beam_reset sets it: prompt [B, P] int64 (numpy or torch)."""
+    """The start of a search as TrainEngine._gen_reset / _beam_reset (kvq/inference.py) set it: prompt [B, P] int64 (numpy or torch)."""
     prompt = np.asarray(prompt, dtype=np.int64)
     R = round_up(B * W, 8) if R is None else R
     own = np.arange(R, dtype=np.int32)

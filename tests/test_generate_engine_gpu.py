@@ -103,6 +103,32 @@ def test_generated_tokens_are_the_argmax_of_the_teacher_forced_logits(kind, dtyp
     assert torch.equal(G[:, 1:].cpu(), gen["logits"].cpu().argmax(-1))
 
 
+def test_per_layer_cross_attention_fill_with_one_frozen_key_weight():
+    """One decoder layer's cross-attention key weight frozen before the engine is built: ca.k / ca.v are no longer uniformly
+    trainable, so generate / beam_search fill the cross-attention keys | values with one GEMM per layer instead of one for all.
+    f32, the file's own B, Se, L, P = 1; the rules of test_generated_tokens_are_the_argmax_... on that arm."""
+    from kvq.engine import engine_of
+    model = build("shelgon")
+    lat32, _ = latents_of("shelgon", model, SEED)
+    model.decoder.bert.encoder.layer[0].crossattention.self.key.weight.requires_grad_(False)
+    model = model.cuda().eval()
+    eng = engine_of(model)
+    assert eng.dtype == torch.float32 and eng._cakv_batched is False
+    lat = lat32.cuda().contiguous()
+    prompt = torch.full((B, 1), START, dtype=torch.int64, device="cuda")
+    with torch.no_grad():
+        gen = eng.generate(lat, L, prompt, want_logits=True)
+        G = gen["ids"]
+        tf = eng.decode(lat, G, torch.ones_like(G), want_logits=True)["logits"].float()[:, :L - 1]
+        one = eng.beam_search(lat, L, prompt, num_beams=1)
+    assert G.shape == (B, L) and gen["logits"].shape == (B, L - 1, V)
+    dist = (gen["logits"] - tf).abs()
+    print(f"\n[generate, per-layer keys | values fill] max |step logits - teacher-forced logits| = {float(dist.max()):.3e}")
+    assert bool((dist <= 2 * (ATOL + RTOL * tf.abs())).all())
+    assert torch.equal(G[:, 1:].cpu(), gen["logits"].cpu().argmax(-1))
+    assert torch.equal(one["ids"], G)
+
+
 @pytest.mark.parametrize("kind", ["shelgon", "bagon"])
 def test_f32_step_logits_against_huggingface(kind):
     c = case(kind, torch.float32)
